@@ -16,7 +16,15 @@ Other configs behind --config (BASELINE.json configs[i] is --config i+1):
   --config 5: configs[4], 2-camera rig + IMU on a cubic B-spline pose trajectory, 1200 frames at 20 Hz, 200 Hz
               IMU, 50 knots/s; one step = one GN pass of the spline system.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+A plain run sets up, warms up, times the --steps passes and prints the result line (metric, value, unit,
+ms_per_step, ...).  --full adds what takes runs of its own: the build kernel's roofline figures, the per-pass device
+times, the pass breakdown of configs[4] and the CPU baselines (--no-cpu-baseline leaves those out).
+--dump-outputs DIR writes what the timed passes left to the caller, the state after their last step, as
+DIR/state.npy (float64).  The problems are seeded and the timed passes start from a fixed state (the initial state,
+configs[2]: the LM solution; configs[4]: the initial state advanced by the --warmup passes), so two builds run with
+the same arguments can be compared output for output.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -68,6 +76,19 @@ def pmc_traffic_bytes(match, config):
             if match(name):
                 return k["hbm_bytes_per_launch"], os.path.relpath(path, ROOT)
     return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as <directory>/<name>.npy (float32 / float64, at most 64 MB in all)."""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def host_cpu():
@@ -139,12 +160,8 @@ def main_spline(args):
     t0 = time.perf_counter()
     g.run_gn(args.steps)
     wall = time.perf_counter() - t0
-    ks = g.kernel_stats(10)
-    # roofline: the pass's largest single launch, the node assembly (k_sp_assemble); the pass as a whole is bound by
-    # the cyclic reduction's dependent chain of small launches
-    asm_ms, asm_bytes = g.assemble_stats(10)
-    achieved = asm_bytes / (asm_ms * 1e-3) / 1e9
-    pmc = pmc_traffic_bytes(lambda n: n.startswith("ksp::k_sp_assemble("), 5)
+    if args.dump_outputs:  # the state after the last timed pass (warmup + steps GN passes from the initial state)
+        dump_outputs(args.dump_outputs, {"state": g.get_state()})
     value = args.steps / wall
     out = {
         "metric": METRIC, "value": value, "unit": "iterations/s", "n_gpus": 1, "steps": args.steps,
@@ -154,6 +171,24 @@ def main_spline(args):
                    "frames": p.n_frames, "cameras": p.n_cams, "corners": p.n_corners, "imu_samples": p.n_imu,
                    "spline_coefficients": p.n_coeffs, "jacobian_cols": p.total_cols, "camera_block": p.cam_cols,
                    "policy": "gauss_newton", "parallelism": "single GPU"},
+    }
+    if args.full:
+        out.update(spline_kernel_figures(g))
+        if not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline_spline(p)
+            out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
+    print(json.dumps(out))
+
+
+def spline_kernel_figures(g):
+    """--full, configs[4]: the roofline entry and the pass breakdown, from timed runs of their own."""
+    ks = g.kernel_stats(10)
+    # roofline: the pass's largest single launch, the node assembly (k_sp_assemble); the pass as a whole is bound by
+    # the cyclic reduction's dependent chain of small launches (DESIGN.md 10)
+    asm_ms, asm_bytes = g.assemble_stats(10)
+    achieved = asm_bytes / (asm_ms * 1e-3) / 1e9
+    pmc = pmc_traffic_bytes(lambda n: n.startswith("ksp::k_sp_assemble("), 5)
+    return {
         "roofline": {"bound": "hbm", "kernel": "k_sp_assemble", "achieved": achieved, "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      "traffic": (pmc[0] / (asm_ms * 1e-3) / 1e9) if pmc else None,
@@ -166,10 +201,6 @@ def main_spline(args):
                                          "bound": "dependent launch chain (per-level latency)"}},
         "pass_breakdown_ms": {k: v for k, v in ks.items() if k.endswith("_ms")},
     }
-    if not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline_spline(p)
-        out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
-    print(json.dumps(out))
 
 
 def main():
@@ -179,7 +210,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", type=int, default=4, choices=[2, 3, 4, 5],
                     help="BASELINE.json configs[i] is --config i+1 (default 4: the north-star 8-cam x 2000-frame rig)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the build kernel's roofline figures, "
+                         "per-pass device times (configs[4]: the pass breakdown) and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the state the timed passes end at as DIR/state.npy (float64; rank r > 0 of a multi-GPU "
+                         "run writes its shard's state as DIR/state_rank<r>.npy)")
     ap.add_argument("--comm", action="store_true",
                     help="N=1 through the multi-GPU path: rendezvous, a one-rank RCCL communicator, captured RCCL")
     ap.add_argument("--shard-of", type=int, default=0, metavar="K",
@@ -247,6 +284,9 @@ def main():
     extra = 8 * max(1, int(np.ceil(WARM_MS * 1e-3 / max(t8, 1e-6))))
     if extra > 8:
         g.run_gn(extra - 8)
+    # the number of warm-up passes above follows the clock: the timed passes start from the seeded start state again
+    # (same pass cost), so that what they compute is the same from run to run (--dump-outputs)
+    g.set_state(shard.state_init if gn_start is None else gn_start)
     graphed = g.gn_prepare(args.steps)  # loop start + every graph the timed passes launch, captured and uploaded
     if grp:
         grp.barrier()
@@ -257,16 +297,20 @@ def main():
     py_wall = time.perf_counter() - t0
     wall = grp.max(sec) if grp else sec
 
-    # dominant kernel (the build) timing with HIP events on the handle's stream, inside GN passes; the per-pass device
-    # time of iterations 1..20 from HIP events at every pass start inside one captured graph (the
-    # median of iterations 2..20, iteration 1 reported on its own)
-    build_ms, bytes_per, flops_per = g.build_kernel_stats()
-    kname = g.build_kernel_name()
-    pass_ms, _ = g.gn_pass_times(20)
-    pass_med = float(np.median(pass_ms[1:]))
-    achieved = bytes_per / (build_ms * 1e-3) / 1e9
-    useful_tfs = flops_per / (build_ms * 1e-3) / 1e12
-    pmc = pmc_traffic_bytes(is_build_kernel, args.config) if (world == 1 and not args.shard_of) else None
+    if args.dump_outputs:  # what the caller of the timed passes holds after them: the state at their last step
+        dump_outputs(args.dump_outputs, {"state" if rank == 0 else "state_rank%d" % rank: g.get_state()})
+
+    if args.full:
+        # dominant kernel (the build) timing with HIP events on the handle's stream, inside GN passes; the per-pass device
+        # time of iterations 1..20 from HIP events at every pass start inside one captured graph (the
+        # median of iterations 2..20, iteration 1 reported on its own)
+        build_ms, bytes_per, flops_per = g.build_kernel_stats()
+        kname = g.build_kernel_name()
+        pass_ms, _ = g.gn_pass_times(20)
+        pass_med = float(np.median(pass_ms[1:]))
+        achieved = bytes_per / (build_ms * 1e-3) / 1e9
+        useful_tfs = flops_per / (build_ms * 1e-3) / 1e12
+        pmc = pmc_traffic_bytes(is_build_kernel, args.config) if (world == 1 and not args.shard_of) else None
 
     sys.stdout.flush()
     os.dup2(stdout_fd, 1)
@@ -291,29 +335,32 @@ def main():
                        "frames_per_gpu": shard.n_frames, "cameras": full.n_cams, "corners_per_gpu": shard.n_corners,
                        "jacobian_cols": full.total_cols, "camera_block": full.cam_cols, "policy": "gauss_newton",
                        "parallelism": f"frame-sharded x{world}"},
-            # the build kernel's arithmetic intensity (SURVEY 8(d) flops / algorithmic bytes: 1.69 GFLOP over 67.6 MB,
-            # ~25 flop/B at configs[3]) is above the FP64 ridge (78.6 TF/s / 8 TB/s ~ 9.8 flop/B): its roofline is the
-            # FP64 compute pipe, which the f64 MFMAs and the f64 VALU work of one SIMD share (their issue serialises,
-            # DESIGN.md 3c), so "mfma" names the compute bound.  The HBM view is kept beside.
-            "roofline": {"bound": "mfma", "kernel": kname, "achieved": useful_tfs, "peak": FP64_PEAK_TFS,
-                         "unit": "TFLOP/s", "frac": useful_tfs / FP64_PEAK_TFS,
-                         "traffic": pmc[0] if pmc else None, "traffic_source": pmc[1] if pmc else None,
-                         "avg_ms": build_ms, "algorithmic_flops": flops_per, "algorithmic_bytes": bytes_per,
-                         "arithmetic_intensity": flops_per / bytes_per,
-                         "limiter": "the SIMD's FP64 pipe (f64 MFMA + f64 VALU issue of the view waves, serialised) "
-                                    "and the per-frame dependency chain (SQ counters, DESIGN.md 3c, 6)",
-                         "hbm": {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                 "frac": achieved / HBM_PEAK_GBS,
-                                 "traffic_gbs": (pmc[0] / (build_ms * 1e-3) / 1e9) if pmc else None}},
-            "per_pass_median_ms": pass_med, "first_pass_ms": float(pass_ms[0]),
-            "per_pass_ms": [round(float(x), 5) for x in pass_ms],
-            "useful_fp64_tflops": flops_per / (pass_med * 1e-3) / 1e12,
             "library_seconds": sec, "python_wall_seconds": py_wall,
             "device_warmup": {"warmup_passes": args.warmup, "clock_warmup_passes": extra, "min_ms": WARM_MS},
             "comm": {"rccl": bool(use_comm), "ranks": world, "rendezvous": "stdlib TCP" if use_comm else None,
                      "graphed": int(graphed)},
         }
-        if not args.no_cpu_baseline:
+        if args.full:
+            out.update({
+                # the build kernel's arithmetic intensity (SURVEY 8(d) flops / algorithmic bytes: 1.69 GFLOP over 67.6 MB,
+                # ~25 flop/B at configs[3]) is above the FP64 ridge (78.6 TF/s / 8 TB/s ~ 9.8 flop/B): its roofline is the
+                # FP64 compute pipe, which the f64 MFMAs and the f64 VALU work of one SIMD share (their issue serialises,
+                # DESIGN.md 3c), so "mfma" names the compute bound.  The HBM view is kept beside.
+                "roofline": {"bound": "mfma", "kernel": kname, "achieved": useful_tfs, "peak": FP64_PEAK_TFS,
+                             "unit": "TFLOP/s", "frac": useful_tfs / FP64_PEAK_TFS,
+                             "traffic": pmc[0] if pmc else None, "traffic_source": pmc[1] if pmc else None,
+                             "avg_ms": build_ms, "algorithmic_flops": flops_per, "algorithmic_bytes": bytes_per,
+                             "arithmetic_intensity": flops_per / bytes_per,
+                             "limiter": "the SIMD's FP64 pipe (f64 MFMA + f64 VALU issue of the view waves, serialised) "
+                                        "and the per-frame dependency chain (SQ counters, DESIGN.md 3c, 6)",
+                             "hbm": {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                     "frac": achieved / HBM_PEAK_GBS,
+                                     "traffic_gbs": (pmc[0] / (build_ms * 1e-3) / 1e9) if pmc else None}},
+                "per_pass_median_ms": pass_med, "first_pass_ms": float(pass_ms[0]),
+                "per_pass_ms": [round(float(x), 5) for x in pass_ms],
+                "useful_fp64_tflops": flops_per / (pass_med * 1e-3) / 1e12,
+            })
+        if args.full and not args.no_cpu_baseline:
             if strong:  # the whole problem on the host cores (configs[3]: ~0.2 s per iteration at 16 threads)
                 lab = {4: "configs[3] (full 8-cam 2000-frame problem", 3: "configs[2] (full 4-cam 1000-frame problem"}
                 # configs[2]: both sides time GN from the same (post-LM) state

@@ -6,7 +6,7 @@ cd $R; export TMPDIR=/tmp
 O=gpurun_out/it; rm -rf $O; mkdir -p $O
 timeout -k 10 400 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $O/gputests.log 2>&1 || { tail -40 $O/gputests.log; exit 1; }
 tail -3 $O/gputests.log
-timeout -k 10 200 python3 bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { cat $O/bench.err; exit 1; }
+timeout -k 10 200 python3 bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { cat $O/bench.err; exit 1; }
 cat $O/bench.json
 timeout -k 10 200 python3 tools/diag_bstamps.py 4 > $O/bst.log 2>&1 || { cat $O/bst.log; exit 1; }
 tail -45 $O/bst.log

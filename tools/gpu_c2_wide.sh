@@ -7,8 +7,8 @@ cd $R; export TMPDIR=/tmp
 O=gpurun_out/c2; rm -rf $O; mkdir -p $O
 timeout -k 10 400 python -u -m pytest tests -m gpu -x -q --timeout 150 --timeout-method thread > $O/gputests.log 2>&1 || { tail -30 $O/gputests.log; exit 1; }
 tail -2 $O/gputests.log
-KB_BUILDP_WIDE=0 timeout -k 10 200 python3 bench.py --config 3 --no-cpu-baseline > $O/bench_w0.json 2> $O/bench_w0.err || { cat $O/bench_w0.err; exit 1; }
-timeout -k 10 200 python3 bench.py --config 3 --no-cpu-baseline > $O/bench_w1.json 2> $O/bench_w1.err || { cat $O/bench_w1.err; exit 1; }
+KB_BUILDP_WIDE=0 timeout -k 10 200 python3 bench.py --full --config 3 --no-cpu-baseline > $O/bench_w0.json 2> $O/bench_w0.err || { cat $O/bench_w0.err; exit 1; }
+timeout -k 10 200 python3 bench.py --full --config 3 --no-cpu-baseline > $O/bench_w1.json 2> $O/bench_w1.err || { cat $O/bench_w1.err; exit 1; }
 python3 -c "
 import json
 for t in ('w0','w1'):

@@ -11,10 +11,10 @@ if [ "$1" != "none" ]; then
   tail -1 $O/gputests.log
 fi
 for S in 200 20; do
-  timeout -k 10 200 python3 bench.py --no-cpu-baseline --steps $S --warmup 5 > $O/bench$S.json 2> $O/bench$S.err || { cat $O/bench$S.err; exit 1; }
+  timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --steps $S --warmup 5 > $O/bench$S.json 2> $O/bench$S.err || { cat $O/bench$S.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench$S.json')); print('bench$S', round(d['value'],1), d['ms_per_step'], d['per_pass_median_ms'], d['roofline']['avg_ms'], d['roofline']['frac'])"
 done
-timeout -k 10 200 python3 bench.py --shard-of 8 --no-cpu-baseline --steps 200 --warmup 5 > $O/shard8.json 2> $O/shard8.err || { tail -20 $O/shard8.err; exit 1; }
+timeout -k 10 200 python3 bench.py --full --shard-of 8 --no-cpu-baseline --steps 200 --warmup 5 > $O/shard8.json 2> $O/shard8.err || { tail -20 $O/shard8.err; exit 1; }
 python3 -c "import json; d=json.load(open('$O/shard8.json')); print('shard8', round(d['value'],1), d['per_pass_median_ms'], d['roofline']['avg_ms'])"
 if [ "${PROF:-0}" = 1 ]; then
   timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o bench -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline > $O/prof.log 2>&1 || exit $?

@@ -12,6 +12,6 @@ for v in 0 1; do
   echo "== KSP_BACK2=$v"; grep -A30 "^rep 2" $O/levels_b$v.log | grep "elim\|level\|back\|total\|tile"
 done
 for v in 0 1; do
-  KSP_BACK2=$v timeout -k 10 200 python3 bench.py --config 5 --no-cpu-baseline > $O/bench_b$v.json 2> $O/bench_b$v.err || { cat $O/bench_b$v.err; exit 1; }
+  KSP_BACK2=$v timeout -k 10 200 python3 bench.py --full --config 5 --no-cpu-baseline > $O/bench_b$v.json 2> $O/bench_b$v.err || { cat $O/bench_b$v.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench_b$v.json')); print('back2=$v', round(d['value'],1), d['pass_breakdown_ms'])"
 done

@@ -16,13 +16,13 @@ if [ "${PART:-A}" = A ]; then
     timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { cat $O/smoke.log; exit 1; }
     tail -1 $O/smoke.log
   fi
-  timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err || { cat $O/bench.err; exit 1; }
+  timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err || { cat $O/bench.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench.json')); print('bench', d['value'], d['per_pass_median_ms'], d['roofline']['avg_ms'], d.get('cpu_baseline',{}).get('value'))"
-  timeout -k 10 300 python3 bench.py --config 5 > $O/bench_c5.json 2> $O/bench_c5.err || { cat $O/bench_c5.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --config 5 > $O/bench_c5.json 2> $O/bench_c5.err || { cat $O/bench_c5.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench_c5.json')); print('c5', d['value'], d['pass_breakdown_ms'])"
-  timeout -k 10 300 python3 bench.py --config 3 > $O/bench_c3.json 2> $O/bench_c3.err || { cat $O/bench_c3.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --config 3 > $O/bench_c3.json 2> $O/bench_c3.err || { cat $O/bench_c3.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench_c3.json')); print('c3', d['value'], d['roofline']['frac'])"
-  timeout -k 10 200 python3 bench.py --shard-of 8 --no-cpu-baseline > $O/shard8.json 2> $O/shard8.err || { tail -20 $O/shard8.err; exit 1; }
+  timeout -k 10 200 python3 bench.py --full --shard-of 8 --no-cpu-baseline > $O/shard8.json 2> $O/shard8.err || { tail -20 $O/shard8.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/shard8.json')); print('shard8', d['value'], d['per_pass_median_ms'], d['roofline']['avg_ms'])"
   exit 0
 fi

@@ -6,7 +6,7 @@ cd $R; export TMPDIR=/tmp
 O=gpurun_out/sp; rm -rf $O; mkdir -p $O
 timeout -k 10 300 python -u -m pytest tests/test_gpu_spline.py -x -q --timeout 200 --timeout-method thread > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -2 $O/tests.log
-timeout -k 10 200 python3 bench.py --config 5 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { cat $O/bench.err; exit 1; }
+timeout -k 10 200 python3 bench.py --full --config 5 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { cat $O/bench.err; exit 1; }
 cat $O/bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o bench -- python3 bench.py --config 5 --steps 50 --warmup 5 --no-cpu-baseline > $O/prof.log 2>&1 || exit $?
 python3 tools/prof_summary.py $O/prof > $O/sum.txt; head -14 $O/sum.txt
