@@ -44,6 +44,15 @@ __device__ __forceinline__ int cam_arg(const int (&a)[KB_MAX_CAMS], int i) {
   return v;
 }
 
+// row i of the pair index ij = i (i - 1) / 2 + j (j < i, i >= 1), branch-free for i < KB_MAX_CAMS: a search loop
+// would put the loads it indexes into a loop of their own, outside the round they belong to
+__device__ __forceinline__ int pair_row(int ij) {
+  int i = 1;
+#pragma unroll
+  for (int k = 1; k < KB_MAX_CAMS - 1; ++k) i += (ij >= k * (k + 1) / 2) ? 1 : 0;
+  return i;
+}
+
 // broadcast of a double from a wave-uniform lane (v_readlane_b32 x2, no LDS round trip)
 __device__ __forceinline__ double readlane_d(double v, int lane) {
   const unsigned long long b = __double_as_longlong(v);
@@ -801,6 +810,9 @@ __device__ __forceinline__ bool frame_ldl_cols(const KbDev& d, int f, const doub
 }
 
 // dx_f = b_f - A_f dx_c.  Lane slot sl holds column lane + 64 sl of A_f (zero beyond C); lanes 0..5 hold b_f.
+// MASK = false leaves the clamped lanes (column >= C) as loaded, for a caller that pins the loads first and calls
+// fdx_mask after the pins (a select on the loaded value is a wait in front of every load issued after it)
+template <bool MASK = true>
 __device__ __forceinline__ void fdx_load(const KbDev& d, int f, int lane, double (&ar)[6][2], double& bq) {
   const int C = d.C;
 #pragma unroll
@@ -809,10 +821,19 @@ __device__ __forceinline__ void fdx_load(const KbDev& d, int f, int lane, double
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
       const double v = d.Af[((size_t)f * 6 + r) * C + qc];
-      ar[r][sl] = q < C ? v : 0.0;
+      ar[r][sl] = (!MASK || q < C) ? v : 0.0;
     }
   }
   bq = d.bf[(size_t)f * 6 + min(lane, 5)];
+}
+__device__ __forceinline__ void fdx_mask(int C, int lane, double (&ar)[6][2], double (&dxv)[2]) {
+#pragma unroll
+  for (int sl = 0; sl < 2; ++sl) {
+    const bool in = lane + 64 * sl < C;
+    dxv[sl] = in ? dxv[sl] : 0.0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) ar[r][sl] = in ? ar[r][sl] : 0.0;
+  }
 }
 
 // every lane ends with all six entries of dx_f
@@ -1341,40 +1362,33 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
   const bool vw = wave < N;  // view wave (camera = wave) | frame wave fw = wave - N
   const int cam = __builtin_amdgcn_readfirstlane(vw ? wave : 0), fw = __builtin_amdgcn_readfirstlane(wave - N);
   if (wave == 0) KB_TSB(d, 0);
-  // ---- round 1: launch-independent loads, unconditional (clamped) and pinned before the gate
-  const KbCtrl cin = *c;
-  const int done = cin.done, dob = cin.do_build, cur = cin.cur;
-  const double lam = gate ? cin.lambda : d.host_lambda;
+  // ---- round 1: launch-independent loads, unconditional (clamped); all of them are issued before the first pin (a
+  // pin is a wait: loads placed after it start only once the pinned value has arrived), the pins sit before the gate
+  // The control block and the frame-view entry have wave-uniform addresses; the compiler makes such loads scalar
+  // (v_readfirstlane) where they are issued, which waits for them ahead of every later load.  A per-lane zero it
+  // cannot see through keeps them vector loads until they are taken, after the pins.
+  int zl = 0;
+  asm("" : "+v"(zl));
+  const KbCtrl* cv = c + zl;
+  const int c_done = cv->done, c_dob = cv->do_build, c_cur = cv->cur, c_have = cv->have_dx;
+  const double c_lam = cv->lambda;
   const bool tg_lds = d.bp_tg;  // the host decides (its LDS budget holds a second view-output buffer)
   const int nt3 = 3 * d.K;
   constexpr int kTgU = 2;
   double tv[kTgU];
 #pragma unroll
   for (int u = 0; u < kTgU; ++u) tv[u] = d.target[min(tid + u * nth, nt3 - 1)];
-  int2 fv = d.fview[(size_t)f0 * N + cam];
-#pragma unroll
-  for (int u = 0; u < kTgU; ++u) KB_KEEP(tv[u]);
-  KB_KEEPS(fv.x);
-  KB_KEEPS(fv.y);
+  const int2 fvl = d.fview[(size_t)f0 * N + cam + zl];
+  // this thread's column-table entry (a run-time-indexed kernel argument: the compiler reads it with a vector load)
+  const int ctv = (tid < N) ? cam_arg(d.col_intr, tid) : cam_arg(d.col_base, tid - N);
   // GN fused: the previous solve's frame steps are applied here, and H_ff / H_fc are not stored (only the per-call
   // path reads them back: kb_build, k_schur, k_pcg; the fused pass consumes A_f, b_f and the Schur sums)
   const bool gfu = GNF && gate;
   double yr[6][2], dxv[2] = {0.0, 0.0}, bq = 0.0;
   if (gfu) {
 #pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-      const int q = lane + 64 * sl;
-      const double v = d.dx[min(q, C - 1)];
-      dxv[sl] = q < C ? v : 0.0;
-    }
-    fdx_load(d, f0 + min(wave, G - 1), lane, yr, bq);  // wave j steps frame f0 + j (its rows in this round)
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-      KB_KEEP(dxv[sl]);
-#pragma unroll
-      for (int r = 0; r < 6; ++r) KB_KEEP(yr[r][sl]);
-    }
-    KB_KEEP(bq);
+    for (int sl = 0; sl < 2; ++sl) dxv[sl] = d.dx[min(lane + 64 * sl, C - 1)];  // masked after the pins (fdx_mask)
+    fdx_load<false>(d, f0 + min(wave, G - 1), lane, yr, bq);  // wave j steps frame f0 + j (its rows in this round)
   }
   // the state-slot-indexed loads (camera chains and intrinsics of the build state, K_{i,j}, the block's first frame
   // poses) from both ping-pong slots in this round too, picked once the control block is in: one dependent round trip
@@ -1389,9 +1403,7 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int q = min(tid + u * nth, nK - 1), ee = q % 36, ij = q / 36;
-      int i = 1;
-      while (i * (i + 1) / 2 <= ij) ++i;
-      const int j = ij - i * (i - 1) / 2;
+      const int i = pair_row(ij), j = ij - i * (i - 1) / 2;
 #pragma unroll
       for (int sl = 0; sl < 2; ++sl) kv[sl][u] = nK > 0 ? cam_K(d, sl)[(size_t)(i * N + j) * 36 + ee] : 0.0;
     }
@@ -1400,6 +1412,22 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
     for (int sl = 0; sl < 2; ++sl)
 #pragma unroll
       for (int q = 0; q < 7; ++q) fps[sl][q] = d.state[(size_t)sl * d.S + d.off_frame + 7 * fj + q];
+    // the pins, in issue order
+    KB_KEEP(ctv);
+#pragma unroll
+    for (int u = 0; u < kTgU; ++u) KB_KEEP(tv[u]);
+    KB_KEEP(c_lam);
+    KB_KEEP(fvl.x);
+    KB_KEEP(fvl.y);
+    if (gfu) {
+#pragma unroll
+      for (int sl = 0; sl < 2; ++sl) {
+        KB_KEEP(dxv[sl]);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) KB_KEEP(yr[r][sl]);
+      }
+      KB_KEEP(bq);
+    }
 #pragma unroll
     for (int sl = 0; sl < 2; ++sl) {
       KB_KEEP(csv[sl]);
@@ -1408,15 +1436,22 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
 #pragma unroll
       for (int q = 0; q < 7; ++q) KB_KEEP(fps[sl][q]);
     }
+    if (gfu) fdx_mask(C, lane, yr, dxv);
   }
+  const int done = __builtin_amdgcn_readfirstlane(c_done), dob = __builtin_amdgcn_readfirstlane(c_dob);
+  const int cur = __builtin_amdgcn_readfirstlane(c_cur);
+  const double lam = gate ? c_lam : d.host_lambda;
+  int2 fv;
+  fv.x = __builtin_amdgcn_readfirstlane(fvl.x);
+  fv.y = __builtin_amdgcn_readfirstlane(fvl.y);
   if (gate && (done || !dob)) return;
-  const bool upd = gfu && cin.have_dx;
+  const bool upd = gfu && __builtin_amdgcn_readfirstlane(c_have);
   const int bs = upd ? 1 - cur : cur;
   // ---- round 2: loads indexed by round 1
   const double* sf = d.state + (size_t)cur * d.S;
   double* snew = d.state + (size_t)(1 - cur) * d.S;
   if (tid < N * 22) cst[tid / 22][tid % 22] = bs ? csv[1] : csv[0];
-  if (tid < 2 * N) ctab[tid / N][tid % N] = (tid < N) ? cam_arg(d.col_intr, tid) : cam_arg(d.col_base, tid - N);
+  if (tid < 2 * N) ctab[tid / N][tid % N] = ctv;
   // expanded partials (GN fused, C > 64, KbDev::xexp): the block expands its own per-camera sums in the epilogue
   const bool xp = GNF && gfu && fuse && d.xexp;
   if (xp && tid < C) cil[tid] = d.colinfo[tid];
@@ -1438,39 +1473,45 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
     const double* Kc = cam_K(d, bs);
     for (int q = tid + 2 * nth; q < nK; q += nth) {
       const int e = q % 36, ij = q / 36;
-      int i = 1;
-      while (i * (i + 1) / 2 <= ij) ++i;
-      const int j = ij - i * (i - 1) / 2;
+      const int i = pair_row(ij), j = ij - i * (i - 1) / 2;
       Kl[q] = Kc[(size_t)(i * N + j) * 36 + e];
     }
   }
-  KB_KEEPS(cidn);
-  // the previous solve's frame steps: wave j moves frame f0 + j (then f0 + j + NW, ...) and stages its pose
+  // the previous solve's frame steps: wave j moves frame f0 + j (then f0 + j + NW, ...) and stages its pose; the
+  // round-2 loads (cid, y) are in flight meanwhile, pinned after the steps
   double wmax = 0.0;
-  for (int j = wave; j < G; j += NW) {
-    double fp[7];
-    if (j == wave) {
-#pragma unroll
-      for (int q = 0; q < 7; ++q) fp[q] = cur ? fps[1][q] : fps[0][q];
-    } else {
-#pragma unroll
-      for (int q = 0; q < 7; ++q) fp[q] = sf[d.off_frame + 7 * (f0 + j) + q];
-    }
-    if (upd) {
-      if (j == wave) {
-        frame_step(d, f0 + j, true, lane, yr, dxv, bq, fp, snew, wmax);
-      } else {
-        double af[6][2], bfq;
-        fdx_load(d, f0 + j, lane, af, bfq);
-        frame_step(d, f0 + j, true, lane, af, dxv, bfq, fp, snew, wmax);
-      }
-    }
+  auto stage_pose = [&](int j, const double (&fp)[7]) __attribute__((always_inline)) {
     if (lane < 7) {
       double pv = fp[0];
 #pragma unroll
-      for (int q = 1; q < 7; ++q) pv = (lane == q) ? fp[q] : pv;
+      for (int q = 1; q < 7; ++q) {
+        double t = fp[q];
+        asm("" : "+v"(t));  // opaque: the select chain would otherwise become a run-time index into a scratch copy
+        pv = (lane == q) ? t : pv;
+      }
       fpl[8 * j + lane] = pv;
     }
+  };
+  // the wave's first frame, from the round-1 registers, outside the loop: a loop with loads in it waits for every
+  // load in flight at its head, which would put the round-2 round trip in front of this step
+  if (wave < G) {
+    double fp[7];
+#pragma unroll
+    for (int q = 0; q < 7; ++q) fp[q] = cur ? fps[1][q] : fps[0][q];
+    if (upd) frame_step(d, f0 + wave, true, lane, yr, dxv, bq, fp, snew, wmax);
+    stage_pose(wave, fp);
+  }
+  KB_KEEPS(cidn);
+  for (int j = wave + NW; j < G; j += NW) {  // blocks with more frames than waves
+    double fp[7];
+#pragma unroll
+    for (int q = 0; q < 7; ++q) fp[q] = sf[d.off_frame + 7 * (f0 + j) + q];
+    if (upd) {
+      double af[6][2], bfq;
+      fdx_load(d, f0 + j, lane, af, bfq);
+      frame_step(d, f0 + j, true, lane, af, dxv, bfq, fp, snew, wmax);
+    }
+    stage_pose(j, fp);
   }
   if (lane == 0) wmx[wave] = wmax;
   if (tg_lds) {
@@ -4840,12 +4881,31 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
   __shared__ int bflag;                        // CM == 0: baseline x published by the backsolve wave
   __shared__ double xb[CM == 0 ? 128 : 1];     // CM == 0: those x (rows >= 16 pub_tile)
   if (CM == 0 && tid == 0) bflag = 0;
-  const double lam = gate ? c->lambda : d.host_lambda;
-  const double lam2 = lam * lam;
-  int cur = c->cur;
+  // the control block is read once, here, so that its loads go out with the staging round: nothing in this kernel
+  // writes ctrl before finish_prev (which reads and writes *c itself) and the previous kernel has completed, so this
+  // copy equals what a load after the staging barrier would read
+  // copy equals what a load after the staging barrier would read.  The address carries a per-lane zero the compiler
+  // cannot see through: a load from a uniform address is made scalar (v_readfirstlane) right where it is issued, which
+  // waits for it at entry; these stay vector loads until ctrl_take() (CM == 0: behind the staging loads)
+  int zl = 0;
+  asm("" : "+v"(zl));
+  const KbCtrl* cv = c + zl;
+  const int c_cur = cv->cur, c_done = cv->done, c_sok = cv->solve_ok, c_have = cv->have_dx;
+  const double c_lam = cv->lambda;
+  int cur = 0, cdone = 0, csok = 0, bslot = 0;
+  double lam2 = 0.0;
   const bool gfu = gate && d.gn_fused;
-  // GN fused: a pending step means the system was built at the candidate state (slot 1 - cur)
-  const int bslot = (gfu && c->have_dx) ? 1 - cur : cur;
+  auto ctrl_take = [&]() {
+    KB_KEEP(c_lam);
+    cur = __builtin_amdgcn_readfirstlane(c_cur);
+    cdone = __builtin_amdgcn_readfirstlane(c_done);
+    csok = __builtin_amdgcn_readfirstlane(c_sok);
+    // GN fused: a pending step means the system was built at the candidate state (slot 1 - cur)
+    bslot = (gfu && __builtin_amdgcn_readfirstlane(c_have)) ? 1 - cur : cur;
+    const double lam = gate ? c_lam : d.host_lambda;
+    lam2 = lam * lam;
+  };
+  if constexpr (CM > 0) ctrl_take();  // the staging loads are indexed by bslot
   double x[2] = {0.0, 0.0};
   // GN fused: the previous pass's end runs in wave kFinWave while the factorisation runs (CM == 0: wave 2, an
   // update wave, idle during the first panel)
@@ -4869,12 +4929,17 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
     const int q = min(tid + u * nth, 2 * nst - 1), sl = q >= nst ? 1 : 0, e = q - sl * nst;
     cpv[u] = d.state[(size_t)sl * d.S + (e < N * KB_MAX_INTR ? e : d.off_base + e - N * KB_MAX_INTR)];
   }
+  // the per-camera column table entry of this thread: the compiler reads the run-time-indexed kernel argument with a
+  // vector load, which belongs to the staging round too (unconditional; stored below by tid < 3 N)
+  const int ctv = tid < N ? cam_arg(d.nintr, tid) : (tid < 2 * N ? cam_arg(d.col_intr, tid - N) : cam_arg(d.col_base, tid - 2 * N));
   KB_TS(d, 0);
   KB_STAMP(d, 0);
   // phase A: stage K, column info, per-camera sums and the Schur sums in LDS (one row: psum)
   if constexpr (CM == 0) {
     // the k_colimg image (the complete system): one contiguous 16-byte copy, 12 loads in flight per thread (one round
-    // trip for an 8-camera rig); the build's cost (k_colimg) in the same round
+    // trip for an 8-camera rig); the build's cost (k_colimg) in the same round.  The loads are clamped and
+    // unconditional and pinned as a group before the predicated LDS stores: without the pins the compiler moves
+    // each load under its store's bounds check and waits for it there, one round trip per load
     const int n2 = d.img_n >> 1;
     const double2* gi = reinterpret_cast<const double2*>(d.simg);
     double2* li = reinterpret_cast<double2*>(S);
@@ -4887,15 +4952,22 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
       for (int u = 0; u < U; ++u) v[u] = gi[min(q0 + u * nth, n2 - 1)];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
+        KB_KEEP(v[u].x);
+        KB_KEEP(v[u].y);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
         const int q = q0 + u * nth;
         if (q < n2) li[q] = v[u];
       }
     }
     if (tid == 0) cl_red[0] = cb0;
+    ctrl_take();
+    KB_KEEP(ctv);
   } else {
     solve_stage<4, CM, false>(d, bslot, K, Hs, S, bv, ci, tid, nth);
   }
-  if (tid < 3 * N) ctab[tid / N][tid % N] = tid < N ? cam_arg(d.nintr, tid) : (tid < 2 * N ? cam_arg(d.col_intr, tid - N) : cam_arg(d.col_base, tid - 2 * N));
+  if (tid < 3 * N) ctab[tid / N][tid % N] = ctv;
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int q = tid + u * nth;
@@ -4915,10 +4987,10 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
       dxr = bv[n16 + 1 + min(l, nr - 1)];
     }
   }
-  if (tid == 0) okl = (c->solve_ok != 0) && !(bv[C] > 0.0);
-  // the loop's done flag is tested only here: the ctrl and staging loads above went out in one round trip, and
-  // nothing global has been written yet
-  if (gate && c->done) return;
+  if (tid == 0) okl = (csok != 0) && !(bv[C] > 0.0);
+  // the loop's done flag (entry copy) is tested only here, behind the staging loads it was issued with; nothing
+  // global has been written yet
+  if (gate && cdone) return;
   if (gate && !d.gn_fused && tid == 0) c->pending = 1;
   KB_TS(d, 1);
   KB_STAMP(d, 1);

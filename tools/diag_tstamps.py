@@ -8,7 +8,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from kalibr_amd import capi, synth  # noqa: E402
 
-capi.LIB_PATH = os.path.join(ROOT, "kalibr_amd", "libkalibr_hip_stamps.so")
+capi.LIB_PATH = os.path.join(ROOT, "kalibr_amd", os.environ.get("KB_STAMPS_LIB", "libkalibr_hip_stamps.so"))
 L = capi.lib()
 L.kb_diag_read_ts.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.c_int]
 cfg = int(sys.argv[1]) if len(sys.argv) > 1 else 4
