@@ -155,6 +155,15 @@ int kb_get_rhs(kb_handle* h, double* rhs_out);
  * the arrow blocks.  Unsharded handles.  Fails unless the last system came from kb_build: the device-resident
  * loops (kb_optimize, kb_gn_*, kb_build_kernel_stats) overwrite or skip the per-call blocks it reads. */
 int kb_rhs_jtj_rhs(kb_handle* h, double* out);
+/* Optimizer::computeDiagonalCovariances / BlockCholeskyLinearSystemSolver::computeCovarianceBlocks
+ * (aslam_backend/src/Optimizer2.cpp:365-402, BlockCholeskyLinearSystemSolver.cpp:122-148) on the device, from the arrow
+ * structure: Sigma_cc = S^-1, Sigma_fc = -A_f Sigma_cc, Sigma_ff = (H_ff + D_f)^-1 + A_f Sigma_cc A_f^T.
+ * blocks of (J^T J + D)^-1 of the last kb_build under the conditioner in force:
+ * Pcc [C][C], Pff [F][6][6], Pfc [F][6][C] (any may be NULL), canonical column order.
+ * *ok = 0 exactly when kb_solve would report 0 (outputs untouched then).
+ * Always the direct factorisation (kb_set_linear_solver does not matter).  Unsharded handles, C <= 112.  Fails unless
+ * the last system came from kb_build (as kb_rhs_jtj_rhs).  A query: state and system stay as after a kb_solve. */
+int kb_covariance(kb_handle* h, double* Pcc, double* Pff, double* Pfc, int* ok);
 /* CameraCalibrator::PrintReprojectionErrorStatistics (kalibr2/include/kalibr2/CameraCalibrator.hpp:368-411, called per
  * camera after the estimator by kalibr2_ros/src/CalibrateCameras.cpp:318) on the device, for every camera of the
  * handle at its current state: e = y - yhat of every term (ReprojectionError::getPredictedMeasurement), then

@@ -24,7 +24,7 @@ dp = C.POINTER(C.c_double)
 EXPORTS = [
     "kb_create", "kb_destroy", "kb_last_error", "kb_upload_observations", "kb_set_state", "kb_set_state_flat",
     "kb_get_state_flat", "kb_state_size", "kb_num_cols", "kb_camera_cols", "kb_eval_cost", "kb_build",
-    "kb_set_constant_conditioner", "kb_set_conditioner", "kb_solve", "kb_get_rhs", "kb_rhs_jtj_rhs", "kb_reprojection_error_stats", "kb_apply_update", "kb_revert", "kb_get_normal_blocks",
+    "kb_set_constant_conditioner", "kb_set_conditioner", "kb_solve", "kb_get_rhs", "kb_rhs_jtj_rhs", "kb_covariance", "kb_reprojection_error_stats", "kb_apply_update", "kb_revert", "kb_get_normal_blocks",
     "kb_optimize", "kb_get_trace", "kb_run_gn_iterations", "kb_gn_prepare", "kb_gn_launch", "kb_build_kernel_stats",
     "kb_build_kernel_name", "kb_comm_get_unique_id", "kb_gn_pass_times", "kb_append_frames", "kb_drop_last_frames", "kb_optimize_marginal", "kb_optimize_marginal_analyze",
     "kb_comm_init", "kb_comm_init_local", "kb_comm_direct", "kb_xar_export", "kb_xar_test", "kb_selftest_mfma", "kb_solve_marginal", "kb_analyze_marginal",
@@ -122,6 +122,7 @@ def lib():
         L.kb_solve.argtypes = [C.c_void_p, dp, C.POINTER(C.c_int)]
         L.kb_get_rhs.argtypes = [C.c_void_p, dp]
         L.kb_rhs_jtj_rhs.argtypes = [C.c_void_p, dp]
+        L.kb_covariance.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_int)]
         L.kb_reprojection_error_stats.argtypes = [C.c_void_p, dp]
         L.kb_apply_update.argtypes = [C.c_void_p, dp, dp]
         L.kb_get_normal_blocks.argtypes = [C.c_void_p, dp, dp, dp, dp, dp, dp]
@@ -313,6 +314,24 @@ class Solver:
         v = C.c_double()
         _check(lib().kb_rhs_jtj_rhs(self.h, C.byref(v)))
         return v.value
+
+    def covariance(self, cross=False, out=None):
+        """kb_covariance: blocks of (J^T J + D)^-1 of the last build under the conditioner in force.
+        Returns (ok, dict(Pcc [C][C], Pff [F][6][6][, Pfc [F][6][C] when cross])); the arrays are left as they were
+        (zeros, or the caller's `out` arrays) when ok is False."""
+        Cc = self.C
+        F = (self.ncols - Cc) // 6  # the handle's frames (kb_append_frames / kb_drop_last_frames change them)
+        out = dict(out) if out else {}
+        out.setdefault("Pcc", np.zeros((Cc, Cc)))
+        out.setdefault("Pff", np.zeros((F, 6, 6)))
+        if cross:
+            out.setdefault("Pfc", np.zeros((F, 6, Cc)))
+        else:
+            out.pop("Pfc", None)
+        ok = C.c_int()
+        _check(lib().kb_covariance(self.h, _d(out["Pcc"]), _d(out["Pff"]), _d(out["Pfc"]) if cross else None,
+                                   C.byref(ok)))
+        return bool(ok.value), out
 
     def reprojection_error_stats(self):
         """kb_reprojection_error_stats: per camera [n, mean_u, mean_v, std_u, std_v, rmse] of the current state

@@ -133,6 +133,10 @@ struct kb_handle {
   double* xar_agree_buf = nullptr;  // [2]: this rank's failure flag | the sum over the ranks
   bool buildp_wide = false;  // k_buildp<.., MW = 8> (multi-model rigs with <= 8 waves per block)
   double* rjr = nullptr;     // [F + 1] kb_rhs_jtj_rhs: per-frame terms | result
+  double* cov_cc = nullptr;  // kb_covariance: Sigma_cc [C][C] | Sigma_ff [F][36] | Sigma_fc [F][6][C] (lazily allocated,
+  double* cov_ff = nullptr;  // (re)sized for the current frame count like rjr)
+  double* cov_fc = nullptr;
+  size_t cov_F = 0, cov_fcF = 0;
   int gn_prepared = -1;      // kb_gn_prepare'd pass count, consumed by kb_gn_launch (-1: nothing prepared; every
                              // entry point that changes the state, the graphs or the control block resets it)
   bool sys_valid = false;    // the per-call system of the last kb_build is intact (H_ff, H_fc, g_f, H_cc, g_c): the
@@ -1457,6 +1461,86 @@ int kb_rhs_jtj_rhs(kb_handle* h, double* out) {
   KB_HIP(hipGetLastError());
   KB_HIP(hipMemcpyAsync(out, h->rjr + h->F, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   KB_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// Blocks of (J^T J + D)^-1 of the per-call system (the Schur form of BlockCholeskyLinearSystemSolver::
+// computeCovarianceBlocks): the Schur step and column sums of kb_solve, then k_cov_cam (S -> Sigma_cc, one launch)
+// and k_cov_frames (Sigma_fc, Sigma_ff).  Always the direct factorisation, whatever kb_set_solver chose.
+static const void* cov_cam_fn(int C) {
+  return C <= 16   ? (const void*)k_cov_cam<16>
+         : C <= 24 ? (const void*)k_cov_cam<24>
+         : C <= 32 ? (const void*)k_cov_cam<32>
+         : C <= 48 ? (const void*)k_cov_cam<48>
+         : C <= 64 ? (const void*)k_cov_cam<64>
+                   : (const void*)k_cov_cam<0>;
+}
+
+int kb_covariance(kb_handle* h, double* Pcc, double* Pff, double* Pfc, int* ok) {
+  if (!h || !ok) return fail("kb_covariance: null");
+  if (!h->uploaded) return fail("kb_covariance: no observations");
+  if (sharded(h)) return fail("kb_covariance: per-call quantity of an unsharded handle");
+  if (!h->sys_valid) return fail("kb_covariance: no intact system (call kb_build first; the optimizer loops do "
+                                 "not leave the per-call blocks)");
+  const int C = h->C, F = h->F;
+  if (C > kCovMaxC) return fail("kb_covariance: camera block C > 112 is not supported");
+  KB_HIP(hipSetDevice(h->device));
+  unprepare(h);
+  if (!h->cov_cc && h->alloc(&h->cov_cc, (size_t)C * C)) return fail("kb_covariance: allocation failed");
+  if (h->cov_F < (size_t)F) {  // (re)sized for the current frame count (kb_append_frames grows it)
+    if (regrow(h, &h->cov_ff, (size_t)F * 36, 0)) return -1;
+    h->cov_F = (size_t)F;
+  }
+  if (Pfc && h->cov_fcF < (size_t)F) {
+    if (regrow(h, &h->cov_fc, (size_t)F * 6 * C, 0)) return -1;
+    h->cov_fcF = (size_t)F;
+  }
+  const int one = 1;
+  KB_HIP(hipMemcpyAsync(&h->d.ctrl->solve_ok, &one, sizeof(int), hipMemcpyHostToDevice, h->stream));
+  struct CondScope {  // as kb_solve: the diagonal conditioner enters the frame and camera blocks
+    kb_handle* h;
+    CondScope(kb_handle* hh) : h(hh) { h->d.cond2 = h->use_cond ? h->cond2 : nullptr; }
+    ~CondScope() { h->d.cond2 = nullptr; }
+  } cs(h);
+  if (launch_schur(h, 0)) return -1;
+  if (launch_colsum(h, 0)) return -1;
+  const void* fn = cov_cam_fn(C);
+  const int nct = (C + 15) / 16;
+  const size_t lds_frames = sizeof(double) * ((size_t)C * C + (size_t)kCovWaves * 16 * (16 * nct + 1));
+  // k_cov_cam: the solve's LDS layout + one packed triangle (L or its inverse): behind the layout (C <= 64), or from
+  // the diagonal tiles' inverses on (C > 64: tiles | aux | factored diagonal tiles come first, as in solve_body)
+  const int nb16 = (C + 16) / 16;
+  const int eoff = C <= 64 ? (int)((h->lds_solve + 15) / 16) * 2
+                           : kTileSz * nb16 * (nb16 + 1) / 2 + ((16 * nb16 + 3) & ~1) + nb16 * kTileSz;
+  const size_t lds_cam = std::max(h->lds_solve, sizeof(double) * ((size_t)eoff + (size_t)C * (C + 1) / 2));
+  if (lds_cam > 160 * 1024 || lds_frames > 160 * 1024) return fail("kb_covariance: LDS budget exceeded for this rig");
+  KB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cam));
+  KB_HIP(hipFuncSetAttribute((const void*)k_cov_frames, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_frames));
+  KbDev d = h->d;
+  double* cc = h->cov_cc;
+  int eo = eoff;
+  void* args[] = {(void*)&d, (void*)&cc, (void*)&eo};
+  KB_HIP(hipLaunchKernel(fn, dim3(1), dim3(h->solve_threads), args, lds_cam, h->stream));
+  KB_HIP(hipGetLastError());
+  if (Pff || Pfc) {
+    hipLaunchKernelGGL(k_cov_frames, dim3((F + kCovFrames - 1) / kCovFrames), dim3(64 * kCovWaves), lds_frames, h->stream,
+                       d, (const double*)h->cov_cc, h->cov_ff, Pfc ? h->cov_fc : (double*)nullptr);
+    KB_HIP(hipGetLastError());
+  }
+  // the outputs are written only when the factorisation succeeded: Pcc and Pff (0.7 MB at configs[3]) are staged on
+  // the host until the one stream sync tells ok; Sigma_fc (10 MB there) is not worth a staging copy and is fetched
+  // after it, straight into the caller's buffer
+  int okd = 0;
+  std::vector<double> bcc(Pcc ? (size_t)C * C : 0), bff(Pff ? (size_t)F * 36 : 0);
+  KB_HIP(hipMemcpyAsync(&okd, &h->d.ctrl->solve_ok, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (Pcc) KB_HIP(hipMemcpyAsync(bcc.data(), h->cov_cc, sizeof(double) * bcc.size(), hipMemcpyDeviceToHost, h->stream));
+  if (Pff) KB_HIP(hipMemcpyAsync(bff.data(), h->cov_ff, sizeof(double) * bff.size(), hipMemcpyDeviceToHost, h->stream));
+  KB_HIP(hipStreamSynchronize(h->stream));
+  *ok = okd;
+  if (!okd) return 0;
+  if (Pcc) std::memcpy(Pcc, bcc.data(), sizeof(double) * bcc.size());
+  if (Pff) std::memcpy(Pff, bff.data(), sizeof(double) * bff.size());
+  if (Pfc) KB_HIP(hipMemcpy(Pfc, h->cov_fc, sizeof(double) * (size_t)F * 6 * C, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -44,6 +44,7 @@ constexpr unsigned long long kXarTimeoutTicks = 1000000000ull;  // default wait 
 
 // k_marg (marginal truncated-SVD camera solve, aslam_incremental_calibration LinearSolver)
 constexpr int kMargThreads = 1024;
+constexpr int kCovMaxC = 112;          // kb_covariance: Sigma_cc [C][C] + four waves' product tiles in LDS <= 160 KB
 constexpr int kMargMaxC = 112;         // packed Omega + V in LDS: C(C+1)/2 + C^2 + 2C doubles <= 160 KB
 constexpr int kMargMaxSweeps = 40;
 constexpr double kMargJacobiTol = 1.1102230246251565e-16;  // skip |a_pq| <= 2^-53 sqrt|a_pp a_qq|

@@ -5238,6 +5238,365 @@ __global__ void __launch_bounds__(CM == 0 ? 512 : 256) k_solve(KbDev d, int gate
 }
 
 // ---------------------------------------------------------------------------------------------
+// Covariance blocks of the per-call system (kb_covariance): blocks of (J^T J + D)^-1, D the conditioner in force.
+//   Sigma_cc = S^-1,  Sigma_fc = -A_f Sigma_cc,  Sigma_ff = (H_ff + D_f)^-1 + A_f Sigma_cc A_f^T
+// (the arrow structure; Optimizer::computeDiagonalCovariances / BlockCholeskyLinearSystemSolver::
+// computeCovarianceBlocks).  k_cov_cam (one block) forms and factors S as the per-call k_solve<CM> does (the same
+// staging, expansion and factorisation functions, so the pivots and ctrl->solve_ok agree with kb_solve), then inverts
+// from the factor:  W = L D -> L -> X = L^-1 (one column per 16-lane row, cov_invert_columns), and
+// Sigma_cc[i][j] = sum_{k >= i} X[k][i] X[k][j] / D_k for i >= j, stored to both (i, j) and (j, i).
+// ---------------------------------------------------------------------------------------------
+
+// X = L^-1 of a unit lower triangular L (column-major packed, cidx), one column j per 16-lane row of a wave: lane r
+// holds x_i of the rows i = 16 m + r (m < kCovRM), x_j = 1.  Step k broadcasts the finished x_k within the row
+// and subtracts L[i][k] x_k from the rows i > k (column k of L is contiguous in i).  The four columns of a wave run the
+// same steps: x_k = 0 before a column's own start, so its early steps change nothing.  No barrier, no reduction.
+constexpr int kCovRM = (kCovMaxC + 15) / 16;
+template <int M>
+__device__ __forceinline__ void cov_col_steps(double (&x)[kCovRM], const double* Lc, int C, int r, int k0) {
+  if constexpr (M < kCovRM) {
+    const int row0 = threadIdx.x & 48;  // first lane of this 16-lane row within the wave
+    // rolled (the unrolled 112 steps take every register there is): the broadcast lane is a run-time value
+#pragma unroll 1
+    for (int q = 0; q < 16; ++q) {
+      const int k = 16 * M + q;
+      if (k >= C - 1) break;   // block-uniform: the last column has no rows below it
+      if (k < k0) continue;    // wave-uniform: before the first column of this wave's four
+      const double xk = __shfl(x[M], row0 | q);
+      const double* col = Lc + cidx(0, k, C);
+#pragma unroll
+      for (int mm = M; mm < kCovRM; ++mm) {
+        const int i = 16 * mm + r;
+        const bool in = i > k && i < C;
+        const double l = col[in ? i : k + 1];
+        x[mm] = fma(-(in ? l : 0.0), xk, x[mm]);
+      }
+    }
+    cov_col_steps<M + 1>(x, Lc, C, r, k0);
+  }
+}
+
+__device__ __forceinline__ void cov_invert_columns(const double* Lc, double* Xp, int C, int nth) {
+  const int tid = threadIdx.x, grp = tid >> 4, r = tid & 15, ngrp = nth >> 4;
+#pragma unroll 1
+  for (int j0 = 0; j0 < C; j0 += ngrp) {
+    const int j = j0 + grp, k0 = j0 + (grp & ~3);
+    double x[kCovRM];
+#pragma unroll
+    for (int m = 0; m < kCovRM; ++m) x[m] = (16 * m + r == j) ? 1.0 : 0.0;
+    cov_col_steps<0>(x, Lc, C, r, k0);
+#pragma unroll
+    for (int m = 0; m < kCovRM; ++m) {
+      const int i = 16 * m + r;
+      if (j < C && i > j && i < C) Xp[cidx(i, j, C)] = x[m];
+    }
+  }
+}
+
+// LDS address of the strictly lower entry (i, k), i > k, of the factored camera block: packed column-major (CM > 0),
+// or the tile image with the diagonal tiles in Dfac (CM == 0, ldl_panels)
+template <int CM>
+__device__ __forceinline__ double* cov_lptr(double* S, double* Dfac, int i, int k, int C) {
+  if constexpr (CM > 0) return S + cidx(i, k, C);
+  return (i >> 4) == (k >> 4) ? Dfac + (i >> 4) * kTileSz + (i & 15) * kTS + (k & 15) : S + tidx(i, k);
+}
+
+template <int CM>
+__global__ void __launch_bounds__(CM == 0 ? 512 : 256) k_cov_cam(KbDev d, double* Pcc, int eoff) {
+  if constexpr (CM == 0) KB_MFMA_AGPR();
+  KbCtrl* c = d.ctrl;
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int N = d.N, C = d.C, tid = threadIdx.x, nth = blockDim.x;
+  const int Cp = C * (C + 1) / 2;
+  const int nb = (C + 16) >> 4, n16 = 16 * nb;
+  // the LDS layout of solve_body<CM>
+  double* S = sm;
+  double* bv = S + (CM > 0 ? Cp : kTileSz * nb * (nb + 1) / 2);
+  double* Hs = CM > 0 ? bv + 2 * C + 1 : bv;
+  double* T = CM > 0 ? Hs + N * 256 : bv;
+  double* K = T + N * N * 36;
+  double* Dfac = CM > 0 ? K + N * N * 36 : bv + ((n16 + 2 + 1) & ~1);
+  double* Xinv = Dfac + (CM > 0 ? 0 : nb * kTileSz);
+  double* rDv = Xinv + (CM > 0 ? 0 : nb * kTileSz);
+  int* ci = (int*)(rDv + (CM > 0 ? 0 : n16));
+  __shared__ int okl;
+  __shared__ int ctab[3][KB_MAX_CAMS];
+  __shared__ double rdl[CM > 0 ? CM : kCovMaxC];  // 1 / D
+  const int csok = c->solve_ok, bslot = c->cur;
+  const double lam2 = d.host_lambda * d.host_lambda;
+  if constexpr (CM == 0) {
+    // the k_colimg image (the complete system, conditioner on the diagonal)
+    const int n2 = d.img_n >> 1;
+    const double2* gi = reinterpret_cast<const double2*>(d.simg);
+    double2* li = reinterpret_cast<double2*>(S);
+    constexpr int U = 12;
+#pragma unroll 1
+    for (int q0 = tid; q0 < n2; q0 += U * nth) {
+      double2 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = gi[min(q0 + u * nth, n2 - 1)];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        KB_KEEP(v[u].x);
+        KB_KEEP(v[u].y);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int q = q0 + u * nth;
+        if (q < n2) li[q] = v[u];
+      }
+    }
+  } else {
+    const int ctv = tid < N ? cam_arg(d.nintr, tid) : (tid < 2 * N ? cam_arg(d.col_intr, tid - N) : cam_arg(d.col_base, tid - 2 * N));
+    solve_stage<4, CM, false>(d, bslot, K, Hs, S, bv, ci, tid, nth);
+    if (tid < 3 * N) ctab[tid / N][tid % N] = ctv;
+  }
+  __syncthreads();
+  if (tid == 0) okl = (csok != 0) && !(bv[C] > 0.0);  // non-PD frame blocks of the Schur step
+  if constexpr (CM > 0) {
+    for (int q = tid; q < N * N * 36; q += nth) {
+      const int e = q % 36, ik = q / 36, i = ik / N, k = ik % N;
+      double s = 0.0;
+      if (k < i) {
+        const int a = e / 6, b = e % 6;
+#pragma unroll
+        for (int m = 0; m < 6; ++m) s += Hs[i * 256 + a * 16 + m] * K[(i * N + k) * 36 + m * 6 + b];
+      }
+      T[q] = s;
+    }
+    __syncthreads();
+    cam_expand_blocks<CM>(S, C, N, ctab, Hs, T, K, lam2, nth >> 6, d.cond2);
+    __syncthreads();
+    if (tid < 64) {
+      // the rows as ldl_solve_reg takes them (lane i: row i, identity outside C), then the same LDL^T steps
+      const int lane = tid;
+      double row[CM];
+      const int li = lane < C ? lane : 0;
+      const int cs_i = li * (2 * C - li - 1) / 2;
+#pragma unroll
+      for (int j = 0; j < CM; ++j) {
+        const int jc = j < C ? j : 0;
+        const int cs_j = jc * (2 * C - jc - 1) / 2;
+        row[j] = S[(li >= jc) ? cs_j + li : cs_i + jc];
+      }
+#pragma unroll
+      for (int j = 0; j < CM; ++j) KB_KEEP(row[j]);
+#pragma unroll
+      for (int j = 0; j < CM; ++j) {
+        const bool in = lane < C && j < C;
+        row[j] = in ? row[j] : (lane == j ? 1.0 : 0.0);
+      }
+      bool ok = true;
+      double rD = 1.0;
+      ldl_steps<CM, 0, CM>(row, lane, ok, rD);
+      if (!ok) okl = 0;
+      // lane i holds W[i][k] = L[i][k] D_k (k < i): back into the packed lower storage
+#pragma unroll
+      for (int k = 0; k < CM; ++k)
+        if (k < lane && lane < C) S[cidx(lane, k, C)] = row[k];
+      if (lane < CM) rdl[lane] = rD;
+    }
+    __syncthreads();
+  } else {
+    __syncthreads();
+    ldl_panels(d, S, rDv, Dfac, Xinv, C, nb, &okl);  // ends with a block barrier
+  }
+  if (!okl) {  // as kb_solve reports it; Pcc is left alone
+    if (tid == 0) c->solve_ok = 0;
+    return;
+  }
+  if constexpr (CM == 0) {  // 1 / D out of the solve's layout: E below overlaps it
+    for (int i = tid; i < C; i += nth) rdl[i] = rDv[i];
+    __syncthreads();
+  }
+  const double* rd = rdl;
+  // L = W D^-1 (unit lower) and X = L^-1, both column-major packed (cidx): L in place in S (CM > 0) or copied out of
+  // the tiles into the region E (CM == 0); X in the other of the two.  E: behind the solve's layout (CM > 0), or
+  // from the diagonal tiles' inverses on (CM == 0: Xinv, 1 / D and the column table are no longer needed)
+  double* E = sm + eoff;
+  double* Lc = CM > 0 ? S : E;
+  double* Xp = CM > 0 ? E : S;
+  for (int e = tid; e < C * C; e += nth) {
+    const int i = e / C, k = e % C;
+    if (i > k) Lc[cidx(i, k, C)] = *cov_lptr<CM>(S, Dfac, i, k, C) * rd[k];
+  }
+  __syncthreads();  // CM == 0: the tiles are free from here (X overwrites them)
+  cov_invert_columns(Lc, Xp, C, nth);
+  __syncthreads();
+  // Sigma = X^T D^-1 X, lower entries (i >= j), mirrored: both columns of X are contiguous in k
+  for (int e = tid; e < C * C; e += nth) {
+    const int i = e / C, j = e % C;
+    if (j > i) continue;
+    const double* xi = Xp + cidx(0, i, C);
+    const double* xj = Xp + cidx(0, j, C);
+    double s = (j == i ? 1.0 : xj[i]) * rd[i];
+    for (int k = i + 1; k < C; ++k) s += xi[k] * xj[k] * rd[k];
+    Pcc[(size_t)i * C + j] = s;
+    Pcc[(size_t)j * C + i] = s;
+  }
+}
+
+// k_cov_frames: Sigma_fc = -A_f Sigma_cc and Sigma_ff = (H_ff + D_f)^-1 + A_f Sigma_cc A_f^T, kCovFrames frames per
+// block, two per wave.  Sigma_cc is staged once per block in LDS.  Both products run on v_mfma_f64_16x16x4f64: the two
+// frames' A_f (6 rows each) are rows 0..5 and 8..13 of the zero-padded 16-row operand (12 of 16 rows carry work), so
+// T = A Sigma_cc is 28 k-steps x 7 column tiles at C = 112; T goes through a wave-private LDS tile (row = operand
+// row) and T A^T takes the same A registers as its B operand.  The 6 x 6 inverse is an in-register LDL^T with the
+// diagonal frame_gj uses.  Every sum has a fixed order.
+constexpr int kCovWaves = 4, kCovFrames = 2 * kCovWaves;
+constexpr int kCovKS = (kCovMaxC + 3) / 4, kCovCT = (kCovMaxC + 15) / 16;
+__global__ void __launch_bounds__(64 * kCovWaves) k_cov_frames(KbDev d, const double* Pcc, double* Pff, double* Pfc) {
+  KB_MFMA_AGPR();
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  __shared__ double hinv[kCovWaves][2][36];
+  const int C = d.C, F = d.F, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nct = (C + 15) >> 4, nks = (C + 3) >> 2, LDT = 16 * nct + 1;
+  double* Sg = sm;                                   // [C][C] Sigma_cc
+  double* Tw = sm + C * C + wave * 16 * LDT;          // [16][LDT] this wave's T, then [16][17] T A^T
+  const int f0 = blockIdx.x * kCovFrames + 2 * wave;
+  const int r = lane & 15, kq = lane >> 4;
+  const int fr = f0 + (r >> 3), ri = r & 7;          // operand row r: its frame and row
+  const bool rowok = ri < 6 && fr < F;
+  // one round of loads (clamped, unconditional): the operand rows of A_f, H_ff and its diagonal, the solve flag and
+  // the first batch of Sigma_cc; pinned together below
+  double a[kCovKS];
+  {
+    const double* Ar = d.Af + ((size_t)min(fr, F - 1) * 6 + min(ri, 5)) * C;
+#pragma unroll
+    for (int ks = 0; ks < kCovKS; ++ks) a[ks] = Ar[min(4 * ks + kq, C - 1)];
+  }
+  const int fh = min(f0 + (lane & 1), F - 1);       // the frame whose 6 x 6 block this lane inverts
+  double L[6][6], dg[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+#pragma unroll
+    for (int j = 0; j <= i; ++j) L[i][j] = d.Hff[(size_t)fh * 36 + i * 6 + j];
+    dg[i] = d.cond2 ? d.cond2[C + 6 * fh + i] : d.host_lambda * d.host_lambda;
+  }
+  const int sok = d.ctrl->solve_ok;
+  constexpr int U = 8;
+  const int nth = 64 * kCovWaves, nS = C * C;
+#pragma unroll 1
+  for (int q0 = tid; q0 < nS; q0 += U * nth) {
+    double v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = Pcc[min(q0 + u * nth, nS - 1)];
+    if (q0 == tid) {
+#pragma unroll
+      for (int ks = 0; ks < kCovKS; ++ks) KB_KEEP(a[ks]);
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        KB_KEEP(dg[i]);
+#pragma unroll
+        for (int j = 0; j <= i; ++j) KB_KEEP(L[i][j]);
+      }
+      KB_KEEP(sok);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) KB_KEEP(v[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int q = q0 + u * nth;
+      if (q < nS) Sg[q] = v[u];
+    }
+  }
+  if (!sok) return;  // k_cov_cam (or the Schur step) failed: nothing to write
+#pragma unroll
+  for (int ks = 0; ks < kCovKS; ++ks) a[ks] = (rowok && 4 * ks + kq < C) ? a[ks] : 0.0;
+  // (H_ff + D_f)^-1 = L^-T D^-1 L^-1, every index static (frame_ldl's factorisation)
+  {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) L[i][i] += dg[i];
+    double Di[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      double v[6];
+#pragma unroll
+      for (int j = 0; j < k; ++j) v[j] = L[k][j] * L[j][j];
+      double dk = L[k][k];
+#pragma unroll
+      for (int j = 0; j < k; ++j) dk -= L[k][j] * v[j];
+      L[k][k] = dk;
+      Di[k] = recip_d(dk);
+#pragma unroll
+      for (int i = k + 1; i < 6; ++i) {
+        double s = L[i][k];
+#pragma unroll
+        for (int j = 0; j < k; ++j) s -= L[i][j] * v[j];
+        L[i][k] = s * Di[k];
+      }
+    }
+    double X[6][6];  // L^-1 (unit lower)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      X[j][j] = 1.0;
+#pragma unroll
+      for (int i = j + 1; i < 6; ++i) {
+        double s = L[i][j];
+#pragma unroll
+        for (int k = j + 1; k < i; ++k) s += L[i][k] * X[k][j];
+        X[i][j] = -s;
+      }
+    }
+    if (lane < 2) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+          double s = 0.0;
+#pragma unroll
+          for (int k = i; k < 6; ++k) s += X[k][i] * X[k][j] * Di[k];
+          hinv[wave][lane][i * 6 + j] = s;
+        }
+    }
+  }
+  __syncthreads();  // Sigma_cc staged
+  // T = A Sigma_cc
+  v4d acc[kCovCT];
+#pragma unroll
+  for (int ct = 0; ct < kCovCT; ++ct) acc[ct] = v4d{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int ks = 0; ks < kCovKS; ++ks) {
+    if (ks < nks) {  // block-uniform
+      const double* Sk = Sg + min(4 * ks + kq, C - 1) * C;
+#pragma unroll
+      for (int ct = 0; ct < kCovCT; ++ct)
+        if (ct < nct) acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks], Sk[min(16 * ct + r, C - 1)], acc[ct], 0, 0, 0);
+    }
+  }
+  // acc[ct][q]: row kq + 4 q (frame f0 rows 0..5, frame f0 + 1 rows 8..13), column 16 ct + r
+#pragma unroll
+  for (int ct = 0; ct < kCovCT; ++ct) {
+    if (ct < nct) {
+      const int col = 16 * ct + r;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int row = kq + 4 * q, f = f0 + (row >> 3), i = row & 7;
+        Tw[row * LDT + col] = acc[ct][q];
+        if (Pfc && i < 6 && f < F && col < C) Pfc[((size_t)f * 6 + i) * C + col] = -acc[ct][q];
+      }
+    }
+  }
+  KB_WAVE_SYNC();
+  // T A^T: the A operand is T (row r, k from the LDS tile), the B operand A^T[k][r] = a[ks]
+  v4d m = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int ks = 0; ks < kCovKS; ++ks)
+    if (ks < nks) m = __builtin_amdgcn_mfma_f64_16x16x4f64(Tw[r * LDT + 4 * ks + kq], a[ks], m, 0, 0, 0);
+  KB_WAVE_SYNC();  // every lane's T reads are done: the tile is reused
+#pragma unroll
+  for (int q = 0; q < 4; ++q) Tw[(kq + 4 * q) * 17 + r] = m[q];
+  KB_WAVE_SYNC();
+  // Sigma_ff: both (i, j) and (j, i) from the lower entry
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    if (lane < 36 && f0 + q < F) {
+      const int i = lane / 6, j = lane % 6, hi = max(i, j), lo = min(i, j);
+      Pff[(size_t)(f0 + q) * 36 + lane] = hinv[wave][q][hi * 6 + lo] + Tw[(8 * q + hi) * 17 + 8 * q + lo];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_backsub: one wave per frame, kBsFrames frames per block (a 2000-frame problem is 2000 waves, resident in one
 // round).  The wave forms dx_f = b_f - A_f dx_c (6 wave dot products), stores dx and the new pose, then evaluates the
 // cost of the frame's views at the candidate state (evaluateError fused), view after view in 64-corner passes with

@@ -653,6 +653,36 @@ CalibrateCamerasResult calibrateCameras(const std::vector<int32_t>& models,
     sv->initMatrixStructure(sp, false);
     res.reprojectionErrorStatistics = sv->reprojectionErrorStatistics();
   }
+  // how well determined the calibration is: sqrt diag Sigma_cc of the accepted batches' problem at the final state,
+  // lambda = 0.  A convenience beside the calibration: anything that goes wrong here leaves the vector empty
+  if (stages.solver && est.getProblem().n_frames > 0) {
+    try {
+      auto sv = stages.solver();
+      if (sv && sv->supportsCovariance()) {
+        sv->initMatrixStructure(est.getProblem(), false);
+        sv->setConstantConditioner(0.0);
+        sv->buildSystem(16, false);
+        const std::vector<int> dims = backend::canonicalBlockDimensions(models, 0);  // the camera DVs
+        std::vector<std::pair<int, int>> idx;
+        for (size_t i = 0; i < dims.size(); ++i) idx.emplace_back((int)i, (int)i);
+        std::vector<std::vector<double>> blocks;
+        sv->computeCovarianceBlocks(idx, blocks);
+        std::vector<double> sd;
+        bool good = blocks.size() == dims.size();
+        for (size_t i = 0; good && i < dims.size(); ++i) {
+          good = blocks[i].size() == (size_t)dims[i] * dims[i];
+          for (int k = 0; good && k < dims[i]; ++k) {
+            const double v = blocks[i][(size_t)k * dims[i] + k];
+            good = v >= 0.0 && std::isfinite(v);
+            sd.push_back(good ? std::sqrt(v) : 0.0);
+          }
+        }
+        if (good) res.parameterStdDev = sd;
+      }
+    } catch (const std::exception&) {
+      res.parameterStdDev.clear();
+    }
+  }
   return res;
 }
 

@@ -168,6 +168,11 @@ struct CalibrateCamerasResult {
   /// IncrementalEstimator::addBatch restores, IncrementalEstimator.cpp:348-350, 512-518): per camera
   /// [n, mean_u, mean_v, std_u, std_v, rmse], computed by the stage solver (the device for GpuLinearSystemSolver)
   std::vector<std::array<double, 6>> reprojectionErrorStatistics;
+  /// how well determined the calibration is: sqrt of the diagonal of Sigma_cc = the camera block of (J^T J)^-1
+  /// (lambda = 0) of the accepted batches' problem at the final state, camera columns in canonical order
+  /// [intrinsics | baselines].  Filled only when the stage solver supportsCovariance() and the factorisation succeeds;
+  /// empty otherwise (never an error).
+  std::vector<double> parameterStdDev;
 };
 
 /// `estimatorSolver` is the IncrementalEstimator's marginal solver (GpuMarginalLinearSolver in production)

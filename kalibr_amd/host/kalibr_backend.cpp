@@ -22,6 +22,13 @@ void LinearSystemSolver::setConstantConditioner(double diag) {
   _diagonalConditioner.assign(_JCols, diag);  // LinearSystemSolver.cpp:104-107
 }
 
+void LinearSystemSolver::computeCovarianceBlocks(const std::vector<std::pair<int, int>>&,
+                                                 std::vector<std::vector<double>>&) {
+  throw Exception("computeCovarianceBlocks: not supported by this solver");
+}
+
+void LinearSystemSolver::copyHessian(HessianBlocks&) { throw Exception("copyHessian: not supported by this solver"); }
+
 // ---------------------------------------------------------------- design variables and error terms
 namespace {
 using Kind = DesignVariable::Kind;
@@ -156,6 +163,7 @@ TermAssembly assembleTerms(const std::vector<DesignVariable*>& dvs, const std::v
   for (const DesignVariable* dv : order) {
     need(dv->isActive() && dv->columnBase >= 0, "a design variable the terms read is inactive or has no column base");
     for (int k = 0; k < dv->minimalDimensions(); ++k) a.perm.push_back(dv->columnBase + k);
+    a.blockPerm.push_back(dv->blockIndex);
   }
   need(a.perm.size() == ncols_caller, "active design variables that no term reads (the device solves [intrinsics | "
                                       "baselines | target poses] only)");
@@ -227,6 +235,62 @@ void pullDesignVariables(const TermAssembly& a, const std::vector<double>& state
   for (size_t f = 0; f < F; ++f) get_pose(of + 7 * f, a.frameRotation[f], a.frameTranslation[f]);
 }
 
+// ---------------------------------------------------------------- covariance block ranges
+std::vector<int> canonicalBlockDimensions(const std::vector<int32_t>& cam_model, int n_frames) {
+  std::vector<int> dims;
+  for (int32_t m : cam_model) {
+    int a = 0, b = 0;
+    dv_split(m, &a, &b);
+    dims.push_back(a);
+    if (b) dims.push_back(b);
+  }
+  for (size_t j = 0; j + 1 < cam_model.size(); ++j) dims.insert(dims.end(), {3, 3});
+  for (int f = 0; f < n_frames; ++f) dims.insert(dims.end(), {3, 3});
+  return dims;
+}
+
+CovarianceBlockRange covarianceBlockRange(const std::vector<int32_t>& cam_model, int n_frames, int i, int j) {
+  using Ex = LinearSystemSolver::Exception;
+  const std::vector<int> dims = canonicalBlockDimensions(cam_model, n_frames);
+  const int n = (int)dims.size(), ncam = n - 2 * n_frames;
+  if (i < 0 || j < 0 || i >= n || j >= n) throw Ex("computeCovarianceBlocks: block index out of range");
+  // a camera DV: its first camera column; a frame DV: (frame, first row within the frame's 6)
+  auto cam_col = [&](int k) {
+    int c = 0;
+    for (int q = 0; q < k; ++q) c += dims[q];
+    return c;
+  };
+  const bool fi = i >= ncam, fj = j >= ncam;
+  const int frame_i = fi ? (i - ncam) / 2 : -1, frame_j = fj ? (j - ncam) / 2 : -1;
+  CovarianceBlockRange r;
+  r.rows = dims[i];
+  r.cols = dims[j];
+  if (!fi && !fj) {
+    r.source = CovarianceBlockRange::Source::Pcc;
+    r.row0 = cam_col(i);
+    r.col0 = cam_col(j);
+  } else if (fi && fj) {
+    if (frame_i != frame_j)
+      throw Ex("computeCovarianceBlocks: the design variables belong to two different frames; the cross-frame blocks "
+               "Sigma_fg = A_f Sigma_cc A_g^T are not produced");
+    r.source = CovarianceBlockRange::Source::Pff;
+    r.frame = frame_i;
+    r.row0 = 3 * ((i - ncam) % 2);
+    r.col0 = 3 * ((j - ncam) % 2);
+  } else if (fi) {
+    r.source = CovarianceBlockRange::Source::Pfc;
+    r.frame = frame_i;
+    r.row0 = 3 * ((i - ncam) % 2);
+    r.col0 = cam_col(j);
+  } else {
+    r.source = CovarianceBlockRange::Source::PfcTransposed;
+    r.frame = frame_j;
+    r.row0 = cam_col(i);
+    r.col0 = 3 * ((j - ncam) % 2);
+  }
+  return r;
+}
+
 TermLinearSystemSolver::TermLinearSystemSolver(std::shared_ptr<ProblemLinearSystemSolver> inner,
                                                std::vector<double> target)
     : _inner(std::move(inner)), _target(std::move(target)) {
@@ -287,6 +351,30 @@ double TermLinearSystemSolver::applyStateUpdate(const std::vector<double>& dx) {
   return _inner->applyStateUpdate(dc);
 }
 
+void TermLinearSystemSolver::computeCovarianceBlocks(const std::vector<std::pair<int, int>>& blockIndices,
+                                                     std::vector<std::vector<double>>& outBlocks) {
+  // caller block index -> canonical design variable (the columns inside a DV keep their order)
+  std::vector<int> canon(_a.blockPerm.size(), -1);
+  for (size_t k = 0; k < _a.blockPerm.size(); ++k)
+    if (_a.blockPerm[k] >= 0 && (size_t)_a.blockPerm[k] < canon.size()) canon[_a.blockPerm[k]] = (int)k;
+  std::vector<std::pair<int, int>> ci;
+  for (const auto& b : blockIndices) {
+    if (b.first < 0 || b.second < 0 || (size_t)b.first >= canon.size() || (size_t)b.second >= canon.size() ||
+        canon[b.first] < 0 || canon[b.second] < 0)
+      throw Exception("computeCovarianceBlocks: block index out of range");
+    ci.emplace_back(canon[b.first], canon[b.second]);
+  }
+  _inner->computeCovarianceBlocks(ci, outBlocks);
+}
+
+std::vector<int> TermLinearSystemSolver::blockDimensions() const {
+  const std::vector<int> cd = _inner->blockDimensions();
+  std::vector<int> out(cd.size(), 0);
+  for (size_t k = 0; k < cd.size() && k < _a.blockPerm.size(); ++k)
+    if (_a.blockPerm[k] >= 0 && (size_t)_a.blockPerm[k] < out.size()) out[_a.blockPerm[k]] = cd[k];
+  return out;
+}
+
 void TermLinearSystemSolver::pullDesignVariables() const { backend::pullDesignVariables(_a, _inner->state()); }
 
 // ---------------------------------------------------------------- GpuLinearSystemSolver
@@ -335,6 +423,7 @@ void GpuLinearSystemSolver::initMatrixStructure(const CalibrationProblem& p, boo
   _C = (size_t)kb_camera_cols(h);
   _F = (size_t)p.n_frames;
   _N = (size_t)p.n_cams();
+  _models = p.cam_model;
   _rhs.assign(_JCols, 0.0);
   _diagonalConditioner.assign(_JCols, 0.0);
   _conditioner = 0.0;
@@ -396,6 +485,61 @@ double GpuLinearSystemSolver::rhsJtJrhs() {
   double s = 0.0;
   check(kb_rhs_jtj_rhs(static_cast<kb_handle*>(_h), &s), "kb_rhs_jtj_rhs");
   return s;
+}
+
+void GpuLinearSystemSolver::computeCovarianceBlocks(const std::vector<std::pair<int, int>>& blockIndices,
+                                                    std::vector<std::vector<double>>& outBlocks) {
+  if (!_built) throw Exception("computeCovarianceBlocks: buildSystem first");
+  using Src = CovarianceBlockRange::Source;
+  std::vector<CovarianceBlockRange> ranges;
+  bool cross = false;
+  for (const auto& b : blockIndices) {
+    ranges.push_back(covarianceBlockRange(_models, (int)_F, b.first, b.second));
+    cross = cross || ranges.back().source == Src::Pfc || ranges.back().source == Src::PfcTransposed;
+  }
+  std::vector<double> Pcc(_C * _C), Pff(_F * 36), Pfc(cross ? _F * 6 * _C : 0);
+  int ok = 0;
+  check(kb_covariance(static_cast<kb_handle*>(_h), Pcc.data(), Pff.data(), cross ? Pfc.data() : nullptr, &ok),
+        "kb_covariance");
+  if (!ok) throw Exception("Unable to retrieve covariance");  // BlockCholeskyLinearSystemSolver.cpp:138
+  outBlocks.clear();
+  for (const CovarianceBlockRange& r : ranges) {
+    std::vector<double> blk((size_t)r.rows * r.cols);
+    for (int a = 0; a < r.rows; ++a)
+      for (int b = 0; b < r.cols; ++b) {
+        double v = 0.0;
+        switch (r.source) {
+          case Src::Pcc: v = Pcc[(size_t)(r.row0 + a) * _C + r.col0 + b]; break;
+          case Src::Pff: v = Pff[(size_t)r.frame * 36 + (size_t)(r.row0 + a) * 6 + r.col0 + b]; break;
+          case Src::Pfc: v = Pfc[((size_t)r.frame * 6 + r.row0 + a) * _C + r.col0 + b]; break;
+          case Src::PfcTransposed: v = Pfc[((size_t)r.frame * 6 + r.col0 + b) * _C + r.row0 + a]; break;
+        }
+        blk[(size_t)a * r.cols + b] = v;
+      }
+    outBlocks.push_back(std::move(blk));
+  }
+}
+
+void GpuLinearSystemSolver::copyHessian(HessianBlocks& H) {
+  if (!_built) throw Exception("copyHessian: buildSystem first");
+  H.C = _C;
+  H.F = _F;
+  H.Hcc.assign(_C * _C, 0.0);
+  H.Hff.assign(_F * 36, 0.0);
+  H.Hfc.assign(_F * 6 * _C, 0.0);
+  std::vector<double> gf(_F * 6), gc(_C);
+  double cost = 0.0;
+  check(kb_get_normal_blocks(static_cast<kb_handle*>(_h), H.Hff.data(), H.Hfc.data(), gf.data(), H.Hcc.data(), gc.data(),
+                             &cost),
+        "kb_get_normal_blocks");
+  // the squared conditioner on the diagonal (BlockCholeskyLinearSystemSolver.cpp:126-136)
+  for (size_t k = 0; k < _JCols; ++k) {
+    const double d = k < _diagonalConditioner.size() ? _diagonalConditioner[k] : 0.0;
+    if (k < _C)
+      H.Hcc[k * _C + k] += d * d;
+    else
+      H.Hff[((k - _C) / 6) * 36 + ((k - _C) % 6) * 7] += d * d;
+  }
 }
 
 double GpuLinearSystemSolver::applyStateUpdate(const std::vector<double>& dx) {
@@ -614,6 +758,39 @@ SolutionReturnValue Optimizer2::optimize() {
   srv.dJFinal = deltaJ;
   srv.linearSolverFailure = linearSolverFailure;
   return srv;
+}
+
+HessianBlocks Optimizer2::computeHessian(double lambda) {
+  auto solver = _options.linearSystemSolver;
+  if (!solver) throw Exception("The solver is null");
+  solver->evaluateError(_options.nThreads, false);
+  solver->setConstantConditioner(lambda);
+  solver->buildSystem(_options.nThreads, false);
+  HessianBlocks H;
+  solver->copyHessian(H);
+  return H;
+}
+
+std::vector<std::vector<double>> Optimizer2::computeCovarianceBlocks(const std::vector<std::pair<int, int>>& blockIndices,
+                                                                     double lambda) {
+  auto solver = _options.linearSystemSolver;
+  if (!solver) throw Exception("The solver is null");
+  solver->evaluateError(_options.nThreads, false);
+  solver->setConstantConditioner(lambda);
+  solver->buildSystem(_options.nThreads, false);
+  std::vector<std::vector<double>> out;
+  solver->computeCovarianceBlocks(blockIndices, out);
+  return out;
+}
+
+std::vector<std::vector<double>> Optimizer2::computeDiagonalCovariances(double lambda) {
+  auto solver = _options.linearSystemSolver;
+  if (!solver) throw Exception("The solver is null");
+  const size_t n = solver->blockDimensions().size();
+  if (!n) throw Exception("computeCovarianceBlocks: not supported by this solver");
+  std::vector<std::pair<int, int>> idx;
+  for (size_t i = 0; i < n; ++i) idx.emplace_back((int)i, (int)i);
+  return computeCovarianceBlocks(idx, lambda);
 }
 
 SolutionReturnValue Optimizer2::optimizeOnDevice(int syncEvery) {

@@ -27,6 +27,7 @@
 #include <stdexcept>
 #include <string>
 #include <array>
+#include <utility>
 #include <vector>
 
 namespace kalibr_amd {
@@ -58,6 +59,31 @@ struct SolutionReturnValue {  // backend.hpp:11-24
   bool linearSolverFailure = false;
 };
 
+/// The arrow-shaped Hessian of the rig problem in canonical column order [intrinsics | baselines | frames]:
+/// Hcc [C][C], Hff [F][6][6], Hfc [F][6][C] (row-major); the frame-frame blocks of two different frames are zero.
+struct HessianBlocks {
+  size_t C = 0, F = 0;
+  std::vector<double> Hcc, Hff, Hfc;
+};
+
+/// Minimal dimensions of the canonical design-variable sequence: projection | distortion per camera (4 | 4
+/// pinhole-radtan / equidistant, 4 | 1 FOV, 5 | 4 omni-radtan, one DV of 6 EUCM / double sphere, 5 omni), q | t (3 | 3)
+/// per baseline, q | t per frame.
+std::vector<int> canonicalBlockDimensions(const std::vector<int32_t>& cam_model, int n_frames);
+
+/// Where the covariance block of the canonical design-variable pair (i, j) lives in the device's output
+/// (kb_covariance): Pcc rows x columns, frame `frame`'s Pff, its Pfc (frame rows x camera columns), or the transpose
+/// of that (camera rows x frame columns: row0 / rows then index the camera columns).
+struct CovarianceBlockRange {
+  enum class Source { Pcc, Pff, Pfc, PfcTransposed };
+  Source source = Source::Pcc;
+  int frame = -1;
+  int row0 = 0, rows = 0, col0 = 0, cols = 0;
+};
+/// Throws LinearSystemSolver::Exception for an index out of range and for a pair of DVs of two different frames
+/// (Sigma_fg = A_f Sigma_cc A_g^T is not produced).
+CovarianceBlockRange covarianceBlockRange(const std::vector<int32_t>& cam_model, int n_frames, int i, int j);
+
 // ---------------------------------------------------------------- LinearSystemSolver
 class LinearSystemSolver {
  public:
@@ -81,6 +107,20 @@ class LinearSystemSolver {
   /// design-variable update x <- x [+] dx, returns max|dx| (Optimizer2.cpp:290-310)
   virtual double applyStateUpdate(const std::vector<double>& dx) = 0;
   virtual void revertLastStateUpdate() = 0;
+
+  /// true when computeCovarianceBlocks / copyHessian are implemented
+  virtual bool supportsCovariance() const { return false; }
+  /// BlockCholeskyLinearSystemSolver::computeCovarianceBlocks (BlockCholeskyLinearSystemSolver.cpp:122-148): the blocks
+  /// (i, j) of (J^T J + diag^2)^-1 of the last buildSystem under the conditioner in force, i and j design-variable
+  /// indices in the solver's DV order; outBlocks[k] is row-major [dim(i)][dim(j)].  Throws when the factorisation
+  /// fails ("Unable to retrieve covariance") and, by default, when the solver has no covariance path.
+  virtual void computeCovarianceBlocks(const std::vector<std::pair<int, int>>& blockIndices,
+                                       std::vector<std::vector<double>>& outBlocks);
+  /// BlockCholeskyLinearSystemSolver::copyHessian (:150-153) as Optimizer2::computeHessian uses it: the arrow blocks
+  /// of J^T J of the last buildSystem with the squared conditioner on the diagonal, canonical column order
+  virtual void copyHessian(struct HessianBlocks& outH);
+  /// minimal dimensions of the design variables in the solver's DV order (empty: unknown)
+  virtual std::vector<int> blockDimensions() const { return {}; }
 
   size_t JRows() const { return _JRows; }
   size_t JCols() const { return _JCols; }
@@ -150,6 +190,7 @@ std::vector<DesignVariable*> assignColumnBases(const std::vector<DesignVariable*
 struct TermAssembly {
   CalibrationProblem problem;
   std::vector<int> perm;
+  std::vector<int> blockPerm;  // blockPerm[k] = the caller's block index of canonical design variable k
   std::vector<DesignVariable*> projection, distortion;  // per camera (distortion may be null)
   std::vector<DesignVariable*> baseRotation, baseTranslation;  // per baseline
   std::vector<DesignVariable*> frameRotation, frameTranslation;  // per frame, canonical order
@@ -182,6 +223,12 @@ class TermLinearSystemSolver : public LinearSystemSolver {
   double rhsJtJrhs() override { return _inner->rhsJtJrhs(); }  // invariant under the column permutation
   double applyStateUpdate(const std::vector<double>& dx) override;
   void revertLastStateUpdate() override { _inner->revertLastStateUpdate(); }
+  bool supportsCovariance() const override { return _inner->supportsCovariance(); }
+  /// block indices are the caller's (Optimizer2::initialize order); the blocks come back in the caller's DVs
+  void computeCovarianceBlocks(const std::vector<std::pair<int, int>>& blockIndices,
+                               std::vector<std::vector<double>>& outBlocks) override;
+  void copyHessian(HessianBlocks& outH) override { _inner->copyHessian(outH); }  // canonical order
+  std::vector<int> blockDimensions() const override;
   /// the solver's state into the design variables' values
   void pullDesignVariables() const;
   const TermAssembly& assembly() const { return _a; }
@@ -234,6 +281,12 @@ class GpuLinearSystemSolver : public ProblemLinearSystemSolver {
   double rhsJtJrhs() override;
   double applyStateUpdate(const std::vector<double>& dx) override;
   void revertLastStateUpdate() override;
+  bool supportsCovariance() const override { return true; }
+  /// kb_covariance: the pairs are served from Sigma_cc, Sigma_ff or Sigma_fc; two DVs of different frames throw
+  void computeCovarianceBlocks(const std::vector<std::pair<int, int>>& blockIndices,
+                               std::vector<std::vector<double>>& outBlocks) override;
+  void copyHessian(HessianBlocks& outH) override;  // kb_get_normal_blocks + the squared conditioner
+  std::vector<int> blockDimensions() const override { return canonicalBlockDimensions(_models, (int)_F); }
 
   std::vector<double> state() const override;
   std::vector<std::array<double, 6>> reprojectionErrorStatistics() override;  // kb_reprojection_error_stats
@@ -255,6 +308,7 @@ class GpuLinearSystemSolver : public ProblemLinearSystemSolver {
   void* _h = nullptr;
   GpuOptions _opt;
   size_t _C = 0, _F = 0, _N = 0;
+  std::vector<int32_t> _models;
   double _conditioner = 0.0;
   bool _built = false;
   mutable bool _rhs_valid = false;
@@ -443,6 +497,17 @@ class Optimizer2 {
   /// the same loop device-resident (GpuLinearSystemSolver with an LM or GN policy): one captured graph per
   /// pass, the host only polls the done flag every `syncEvery` passes
   SolutionReturnValue optimizeOnDevice(int syncEvery = 0);
+  /// Optimizer2::computeHessian (Optimizer2.cpp:389-402): evaluateError, setConstantConditioner(lambda), buildSystem,
+  /// copyHessian -- the blocks with lambda^2 on the diagonal
+  HessianBlocks computeHessian(double lambda);
+  /// Optimizer2::computeDiagonalCovariances / computeCovarianceBlocks (Optimizer2.cpp:365-380).  The reference's
+  /// Optimizer2 versions throw "Broken"; these follow the working Optimizer::computeDiagonalCovariances /
+  /// BlockCholeskyLinearSystemSolver::computeCovarianceBlocks semantics: the same build as computeHessian, then the
+  /// solver's computeCovarianceBlocks.  Block indices are the solver's design-variable indices; the diagonal version
+  /// returns one block per design variable.
+  std::vector<std::vector<double>> computeDiagonalCovariances(double lambda);
+  std::vector<std::vector<double>> computeCovarianceBlocks(const std::vector<std::pair<int, int>>& blockIndices,
+                                                           double lambda);
   const Optimizer2Options& options() const { return _options; }
   /// per-pass [J, lambda, deltaX, accepted] of the last optimizeOnDevice()
   const std::vector<double>& trace() const { return _trace; }
