@@ -129,8 +129,9 @@ int kb_drop_last_frames(kb_handle* h, int32_t n_frames);
  *                    ranks hold bitwise-identical camera steps, iteration counts and _residual; each rank then
  *                    back-substitutes its own frames.  _residual (and kb_get_pcg_info) are updated only by a
  *                    completed solve: a failed one (*ok = 0) leaves the previous values for the next d0.
- * kb_optimize always uses the direct solve (its passes are captured graphs); the per-call path
- * (kb_build / kb_solve / kb_apply_update, driven by the host Optimizer2) uses the selected solver. */
+ * kb_optimize (LM, GN and dog-leg policies alike) and kb_dogleg_step always use the direct solve (the loop's passes
+ * are captured graphs); the per-call path (kb_build / kb_solve / kb_apply_update, driven by the host Optimizer2) uses
+ * the selected solver. */
 enum kb_linear_solver { KB_SOLVER_SCHUR = 0, KB_SOLVER_PCG = 1, KB_SOLVER_PCG_SCHUR = 2 };
 typedef struct kb_pcg_options {
   double tolerance;           /* _tolerance (LinearSolverPCG default 1e-6) */
@@ -212,13 +213,18 @@ int kb_get_normal_blocks(kb_handle* h, double* Hff, double* Hfc, double* gf, dou
                          double* cost);
 
 /* Device-resident Optimizer2::optimize (Optimizer2.cpp:183-273) with the
- * LevenbergMarquardt (policy 0, LevenbergMarquardtTrustRegionPolicy.cpp:50-113) or
- * GaussNewton (policy 1, GaussNewtonTrustRegionPolicy.cpp:18-39) trust-region policy.
+ * LevenbergMarquardt (policy 0, LevenbergMarquardtTrustRegionPolicy.cpp:50-113),
+ * GaussNewton (policy 1, GaussNewtonTrustRegionPolicy.cpp:18-39) or
+ * DogLeg (policy 2, DogLegTrustRegionPolicy.cpp:11-161; options: kb_set_dogleg_options) trust-region policy.
  * The whole loop (build, Schur solve, update, cost, policy) runs as one hipGraph per
- * iteration; the host synchronises only every `sync_every` iterations. */
+ * iteration; the host synchronises only every `sync_every` iterations.
+ * Policy 2: a pass is the build at lambda = 0 that keeps the arrow blocks (only after an accepted step), the
+ * steepest-descent reduction, the GN solve (only when the SD branch is not taken and no GN step of this system is
+ * held), the step reductions and selection, dx = a g + b dx_gn, the update, the candidate's chains and cost, and the
+ * policy kernel; a rejected step is followed by a pass that neither builds nor solves.  Unsharded handles only. */
 typedef struct kb_optimizer_options {
-  int32_t policy;          /* 0 = levenberg_marquardt, 1 = gauss_newton */
-  double lambda_init;      /* LM lambdaInit (CalibrationTools.hpp:65: 10) */
+  int32_t policy;          /* 0 = levenberg_marquardt, 1 = gauss_newton, 2 = dog_leg */
+  double lambda_init;      /* LM lambdaInit (CalibrationTools.hpp:65: 10); unused for policies 1 and 2 */
   int32_t max_iterations;  /* Optimizer2Options::maxIterations */
   double convergence_dx;   /* convergenceDeltaX */
   double convergence_dj;   /* convergenceDeltaJ */
@@ -252,8 +258,44 @@ int kb_optimize_marginal_analyze(kb_handle* h, const kb_optimizer_options* opts,
                                  kb_solution* out, kb_marginal_info* info, double* sv_out, double* V_out,
                                  kb_marginal_info* analyze_info, double* analyze_sv_out, double* analyze_V_out);
 
-/* Per-pass trace of the last kb_optimize: [J, lambda, deltaX, accepted] x n (returns count). */
+/* Per-pass trace of the last kb_optimize: [J, lambda, deltaX, accepted] x n (returns count).  For policy 2 the
+ * lambda column carries the trust radius delta the pass used. */
 int kb_get_trace(kb_handle* h, double* trace, int32_t cap);
+
+/* DogLegTrustRegionPolicy (aslam_backend/src/DogLegTrustRegionPolicy.cpp:11-161, include/aslam/backend/
+ * DogLegTrustRegionPolicy.hpp) restated statement by statement: rho = get_dJ() / L0 and the radius update (:33-59),
+ * rebuild + steepest descent only after an accepted step (:63-79), SD / GN / DL selection with beta of :118-131 and
+ * L0 of :85, :112, :134 (the first term of :134 is multiplied by the integer expression 1/2 = 0 and is kept at 0).
+ * Two deliberate deviations:
+ *   1. Initial radius.  The reference starts at delta = 0 (:19), so the first step is always DL with beta = 1/2.
+ *      delta_init (default 0: the reference) is what optimizationStarting assigns to delta.
+ *   2. Failed linear solve.  The reference sets gnComputed before it knows the solve succeeded (:60, :94-99), so the
+ *      iteration after a failed solve reads a _dx_gn it never computed.  Here the GN step counts as held only after a
+ *      completed solve; a failed one is a failed iteration without a step and is retried on the next pass. */
+typedef struct kb_dogleg_options {
+  double delta_init; /* trust radius at optimizationStarting (0: the first-iteration rule of :105-107) */
+} kb_dogleg_options;
+/* options of policy 2 for the following kb_optimize calls; NULL selects the defaults */
+int kb_set_dogleg_options(kb_handle* h, const kb_dogleg_options* opts);
+typedef struct kb_dogleg_info {
+  int32_t step_type; /* 0 SD, 1 GN, 2 DL (_stepType) */
+  double delta;      /* the radius as used (delta == 0 in: the first-iteration radius) */
+  double beta;       /* _beta (DL steps; 0 otherwise) */
+  double sd_scale;   /* _sd_scale = |rhs|^2 / rhsJtJrhs */
+  double dx_sd_norm; /* _dx_sd_norm */
+  double dx_gn_norm; /* _dx_gn_norm; 0 if the GN step was not solved */
+  double L0_over_J;  /* the model decrease _L0 over the cost J of the build state (GN: 1, DL: beta (2 - beta)) */
+} kb_dogleg_info;
+/* One solveSystemImplementation (:63-137) of the last kb_build for trust radius delta, on the device: the
+ * steepest-descent reduction, the GN solve (lambda = 0, no conditioner, the direct factorisation; only when the SD
+ * branch is not taken), the selection and the step dx_out [C + 6F] (may be NULL).  delta == 0 applies the
+ * first-iteration rule (:105-107).  *ok = 0 exactly when a needed solve fails (dx_out untouched, info holds the SD
+ * quantities).  A query like kb_solve: the state is untouched and the system stays as after a kb_solve.  Unsharded
+ * handles.  Fails unless the last system came from kb_build (as kb_rhs_jtj_rhs). */
+int kb_dogleg_step(kb_handle* h, double delta, double* dx_out, kb_dogleg_info* info, int* ok);
+/* Per-pass dog-leg trace of the last kb_optimize with policy 2, aligned with kb_get_trace:
+ * [delta, step_type (-1: failed solve), beta, L0, dx_sd_norm, dx_gn_norm] x n (returns count). */
+int kb_get_dogleg_trace(kb_handle* h, double* out, int32_t cap);
 
 /* Benchmark entry: run exactly n_iter Gauss-Newton passes of the device loop (convergence
  * tests disabled), no host sync inside; *seconds = wall time between stream syncs. */

@@ -25,7 +25,7 @@ EXPORTS = [
     "kb_create", "kb_destroy", "kb_last_error", "kb_upload_observations", "kb_set_state", "kb_set_state_flat",
     "kb_get_state_flat", "kb_state_size", "kb_num_cols", "kb_camera_cols", "kb_eval_cost", "kb_build",
     "kb_set_constant_conditioner", "kb_set_conditioner", "kb_solve", "kb_get_rhs", "kb_rhs_jtj_rhs", "kb_covariance", "kb_reprojection_error_stats", "kb_apply_update", "kb_revert", "kb_get_normal_blocks",
-    "kb_optimize", "kb_get_trace", "kb_run_gn_iterations", "kb_gn_prepare", "kb_gn_launch", "kb_build_kernel_stats",
+    "kb_optimize", "kb_get_trace", "kb_set_dogleg_options", "kb_dogleg_step", "kb_get_dogleg_trace", "kb_run_gn_iterations", "kb_gn_prepare", "kb_gn_launch", "kb_build_kernel_stats",
     "kb_build_kernel_name", "kb_comm_get_unique_id", "kb_gn_pass_times", "kb_append_frames", "kb_drop_last_frames", "kb_optimize_marginal", "kb_optimize_marginal_analyze",
     "kb_comm_init", "kb_comm_init_local", "kb_comm_direct", "kb_xar_export", "kb_xar_test", "kb_selftest_mfma", "kb_solve_marginal", "kb_analyze_marginal",
     # block-Jacobi PCG (LinearSolverPCG)
@@ -80,6 +80,18 @@ class PcgOptions(C.Structure):
     _fields_ = [("tolerance", C.c_double), ("max_iterations", C.c_int32), ("absolute_tolerance", C.c_int32)]
 
 
+class DoglegOptions(C.Structure):
+    _fields_ = [("delta_init", C.c_double)]
+
+
+class DoglegInfo(C.Structure):
+    _fields_ = [("step_type", C.c_int32), ("delta", C.c_double), ("beta", C.c_double), ("sd_scale", C.c_double),
+                ("dx_sd_norm", C.c_double), ("dx_gn_norm", C.c_double), ("L0_over_J", C.c_double)]
+
+
+POLICIES = {"lm": 0, "gn": 1, "dogleg": 2}
+
+
 class PcgInfo(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("residual", C.c_double), ("d0", C.c_double)]
 
@@ -128,6 +140,9 @@ def lib():
         L.kb_get_normal_blocks.argtypes = [C.c_void_p, dp, dp, dp, dp, dp, dp]
         L.kb_optimize.argtypes = [C.c_void_p, C.POINTER(OptimizerOptions), C.POINTER(Solution)]
         L.kb_get_trace.argtypes = [C.c_void_p, dp, C.c_int32]
+        L.kb_set_dogleg_options.argtypes = [C.c_void_p, C.POINTER(DoglegOptions)]
+        L.kb_dogleg_step.argtypes = [C.c_void_p, C.c_double, dp, C.POINTER(DoglegInfo), C.POINTER(C.c_int)]
+        L.kb_get_dogleg_trace.argtypes = [C.c_void_p, dp, C.c_int32]
         L.kb_run_gn_iterations.argtypes = [C.c_void_p, C.c_int32, dp]
         L.kb_gn_prepare.argtypes = [C.c_void_p, C.c_int32]
         L.kb_gn_launch.argtypes = [C.c_void_p, C.c_int32, dp]
@@ -382,9 +397,15 @@ class Solver:
         return res, self._minfo(inf, sv, V), a
 
     def optimize(self, policy="lm", lambda0=10.0, max_iterations=200, eps_x=1e-3, eps_j=1.0, sync_every=4,
-                 use_graph=True):
-        o = OptimizerOptions(0 if policy == "lm" else 1, lambda0, max_iterations, eps_x, eps_j, sync_every,
-                             int(use_graph))
+                 use_graph=True, delta_init=0.0):
+        """kb_optimize: policy "lm", "gn" or "dogleg" (an int is passed through; any other string is "gn" as
+        before).  "dogleg": delta_init is the initial trust radius (kb_set_dogleg_options), res["trace"]'s lambda
+        column carries delta and res["dogleg_trace"] holds per pass [delta, step_type, beta, L0, dx_sd_norm,
+        dx_gn_norm]."""
+        pol = policy if isinstance(policy, int) else POLICIES.get(policy, 1)
+        if pol == 2:
+            _check(lib().kb_set_dogleg_options(self.h, C.byref(DoglegOptions(float(delta_init)))))
+        o = OptimizerOptions(pol, lambda0, max_iterations, eps_x, eps_j, sync_every, int(use_graph))
         s = Solution()
         _check(lib().kb_optimize(self.h, C.byref(o), C.byref(s)))
         res = {f: getattr(s, f) for f, _ in Solution._fields_}
@@ -392,7 +413,21 @@ class Solver:
         tr = np.zeros((cap, 4))
         n = _check(lib().kb_get_trace(self.h, _d(tr), cap))
         res["trace"] = tr[:n].copy()
+        if pol == 2:
+            dt = np.zeros((cap, 6))
+            n = _check(lib().kb_get_dogleg_trace(self.h, _d(dt), cap))
+            res["dogleg_trace"] = dt[:n].copy()
         return res
+
+    def dogleg_step(self, delta):
+        """kb_dogleg_step after build(): (ok, dx, info) of one dog-leg step selection for trust radius delta
+        (0: the first-iteration rule).  info: step_type (0 SD, 1 GN, 2 DL), delta as used, beta, sd_scale, dx_sd_norm,
+        dx_gn_norm, L0_over_J."""
+        dx = np.zeros(self.ncols)
+        ok = C.c_int(0)
+        inf = DoglegInfo()
+        _check(lib().kb_dogleg_step(self.h, float(delta), _d(dx), C.byref(inf), C.byref(ok)))
+        return bool(ok.value), dx, {f: getattr(inf, f) for f, _ in DoglegInfo._fields_}
 
     def run_gn(self, n_iter):
         sec = C.c_double()

@@ -19,6 +19,7 @@
 #include "../../include/kalibr_hip.h"
 #include "kb_kernels.hip"
 #include "kb_pcg.hip"
+#include "kb_dogleg.hip"
 
 using namespace kb;
 
@@ -60,6 +61,7 @@ constexpr int kGraphPasses = 8;  // optimizer passes per captured multi-pass gra
 constexpr int kGnOneGraph = 64;  // kb_gn_launch: runs of up to this many GN passes are one graph (with the loop's end)
 constexpr int kXMaxRanks = 64;
 constexpr int kPolicyMarginal = 2;  // graph policy id of kb_optimize_marginal's passes (GN over the marginal solve)   // expanded partials: per-rank max|dx_f| slots in the image's aux area
+constexpr int kPolicyDogleg = 3;   // graph policy id of the dog-leg passes (kb_optimize policy 2)
 constexpr int kLocalMaxRanks = 16;  // kb_comm_init_local group size
 
 // In-process group of sharded handles (kb_comm_init_local): the collectives become device copies between the
@@ -137,6 +139,12 @@ struct kb_handle {
   double* cov_ff = nullptr;  // (re)sized for the current frame count like rjr)
   double* cov_fc = nullptr;
   size_t cov_F = 0, cov_fcF = 0;
+  // dog-leg policy (kb_optimize policy 2, kb_dogleg_step): device state, gate copies of the control block, partials,
+  // the held GN step and the per-pass trace (lazily allocated, (re)sized for the current frame count like rjr)
+  KbDlBuf dl{};
+  size_t dl_F = 0;
+  int dl_trace_cap = 0;
+  kb_dogleg_options dl_opts{0.0};
   int gn_prepared = -1;      // kb_gn_prepare'd pass count, consumed by kb_gn_launch (-1: nothing prepared; every
                              // entry point that changes the state, the graphs or the control block resets it)
   bool sys_valid = false;    // the per-call system of the last kb_build is intact (H_ff, H_fc, g_f, H_cc, g_c): the
@@ -1569,9 +1577,11 @@ static bool gn_fused(const kb_handle* h, int policy) { return policy == 1 && h->
 
 // ev0 / ev1 (optional): HIP events recorded around the build kernel (kb_build_kernel_stats)
 static int enqueue_marg_pass(kb_handle* h);
+static int enqueue_dl_pass(kb_handle* h);
 
 static int enqueue_pass(kb_handle* h, int policy, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
   if (policy == kPolicyMarginal) return enqueue_marg_pass(h);
+  if (policy == kPolicyDogleg) return enqueue_dl_pass(h);
   KbDev& d = h->d;
   auto build = [&]() -> int {
     if (ev0) KB_HIP(hipEventRecord(ev0, h->stream));
@@ -1763,9 +1773,128 @@ static int loop_start(kb_handle* h, const KbOpts& o) {
   return 0;
 }
 
+
+// ---------------------------------------------------------------- dog-leg policy (kb_dogleg.hip)
+// buffers of the dog-leg kernels, sized for the current frame count and `cap` trace rows; a captured graph holds the
+// pointers, so a reallocation drops the graphs
+static int ensure_dl(kb_handle* h, int cap) {
+  KbDlBuf& b = h->dl;
+  if (!b.s) {
+    if (h->alloc(&b.s, 1) || h->alloc(&b.gb, 2)) return fail("dog-leg: allocation failed");
+    b.gs = b.gb + 1;
+  }
+  const int nstep = (h->ncols + 255) / 256;
+  if (h->dl_F < (size_t)h->F) {
+    if (regrow(h, &b.sdpart, 2 * ((size_t)h->F + h->C), 0) || regrow(h, &b.dxgn, (size_t)h->ncols, 0) ||
+        regrow(h, &b.stepmax, (size_t)nstep, 0))
+      return -1;
+    h->dl_F = (size_t)h->F;
+    drop_graphs(h);
+  }
+  if (b.nstep != nstep) {
+    b.nstep = nstep;
+    drop_graphs(h);
+  }
+  if (h->dl_trace_cap < cap) {
+    if (regrow(h, &b.trace, (size_t)kDlTrace * cap, 0)) return -1;
+    h->dl_trace_cap = cap;
+    b.trace_cap = cap;
+    drop_graphs(h);
+  }
+  return 0;
+}
+
+// launches inside the scope see another control block (a gate copy) and / or another step buffer
+struct DlScope {
+  kb_handle* h;
+  KbDev saved;
+  DlScope(kb_handle* hh, KbCtrl* ctrl, double* dx) : h(hh), saved(hh->d) {
+    if (ctrl) h->d.ctrl = ctrl;
+    if (dx) h->d.dx = dx;
+  }
+  ~DlScope() { h->d = saved; }
+};
+
+// One dog-leg pass, every kernel gated on the device control state (no host sync inside):
+//   build at lambda = 0 that keeps H_ff, H_fc, g_f (only after an accepted step) | column sums, H_cc / g_c (gate gb:
+//   rebuilt passes) | SD reduction | camera solve + frame back-substitution into the held GN step, no update (gate gs:
+//   passes that need it) | step reductions + selection | dx = a g + b dx_gn | update | candidate chains | candidate
+//   cost | policy (accept / revert, trace, next prelude).
+// The build is the LM pass's (Schur step fused at the policy's lambda, here 0), so A_f, b_f and the Schur sums of the
+// held system stay valid for a solve on a later pass (the retry after a failed solve).
+static int enqueue_dl_pass(kb_handle* h) {
+  const KbDlBuf b = h->dl;
+  if (launch_build(h, 1, 1)) return -1;
+  const bool from_rows = h->d.Wp <= 2048;
+  {
+    DlScope sc(h, b.gb, nullptr);
+    if (launch_colsum(h, 1, !from_rows)) return -1;
+    KbDev dr = h->d;
+    if (from_rows) {  // k_camexpand sums the stage-1 rows itself, as in the marginal loop
+      dr.psum = dr.part8;
+      dr.psum_rows = kColsumRows;
+    }
+    hipLaunchKernelGGL(k_camexpand, dim3(1), dim3(256), h->lds_camexp, h->stream, dr, 1);
+    KB_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_dl_sd_frames, dim3((h->F + h->C + 3) / 4), dim3(256), 0, h->stream, h->d, b, 1);
+  hipLaunchKernelGGL(k_dl_sd_final, dim3(1), dim3(256), 0, h->stream, h->d, b, 1);
+  KB_HIP(hipGetLastError());
+  {
+    DlScope sc(h, b.gs, b.dxgn);
+    if (launch_solve(h, 1, 0, from_rows) || launch_backsub(h, 1, 0, 0)) return -1;
+  }
+  const int nu = std::max(h->F, h->N * KB_MAX_INTR);
+  hipLaunchKernelGGL(k_dl_select, dim3(1), dim3(256), 0, h->stream, h->d, b, 1);
+  hipLaunchKernelGGL(k_dl_step, dim3(b.nstep), dim3(256), 0, h->stream, h->d, b, 1);
+  hipLaunchKernelGGL(k_dl_update, dim3((nu + 255) / 256), dim3(256), 0, h->stream, h->d, b);
+  hipLaunchKernelGGL(k_dl_chains, dim3(1), dim3(256), 0, h->stream, h->d, b);
+  hipLaunchKernelGGL(k_dl_cost, dim3(h->d.nblk_cost), dim3(256), 0, h->stream, h->d, b);
+  hipLaunchKernelGGL(k_dl_policy, dim3(1), dim3(256), 0, h->stream, h->d, b);
+  KB_HIP(hipGetLastError());
+  return 0;
+}
+
+static int optimize_dogleg(kb_handle* h, const kb_optimizer_options* opts, kb_solution* out) {
+  if (sharded(h)) return fail("kb_optimize: the dog-leg policy (2) runs on unsharded handles only");
+  KB_HIP(hipSetDevice(h->device));
+  const int max_passes = 2 * opts->max_iterations + 1;
+  if (ensure_trace(h, max_passes + 1) || ensure_dl(h, max_passes + 1)) return -1;
+  KbOpts o{2, opts->max_iterations, 0.0, opts->convergence_dx, opts->convergence_dj};
+  if (loop_start(h, o)) return -1;
+  hipLaunchKernelGGL(k_dl_init, dim3(1), dim3(1), 0, h->stream, h->d, h->dl, h->dl_opts.delta_init);
+  KB_HIP(hipGetLastError());
+  const bool graph = opts->use_graph != 0 && graph_ok(h, kPolicyDogleg);
+  const int every = opts->sync_every > 0 ? opts->sync_every : 2 * kGraphPasses;
+  KbCtrl ctrl{};
+  int passes = 0;
+  while (passes < max_passes) {
+    const int n = std::min(every, max_passes - passes);
+    if (launch_passes(h, kPolicyDogleg, n, graph)) return -1;
+    passes += n;
+    KB_HIP(hipMemcpyAsync(&ctrl, h->d.ctrl, sizeof(KbCtrl), hipMemcpyDeviceToHost, h->stream));
+    KB_HIP(hipStreamSynchronize(h->stream));
+    if (ctrl.done) break;
+  }
+  // every pass ends in its own policy kernel: nothing is pending when the loop stops
+  KB_HIP(hipMemcpy(&ctrl, h->d.ctrl, sizeof(KbCtrl), hipMemcpyDeviceToHost));
+  h->cur = ctrl.cur;
+  out->J_start = ctrl.J_start;
+  out->J_final = ctrl.p_J;
+  out->dx_final = ctrl.deltaX;
+  out->dj_final = ctrl.deltaJ;
+  out->iterations = ctrl.iterations;
+  out->failed_iterations = ctrl.failed_iterations;
+  out->linear_solver_failure = ctrl.lin_fail;
+  out->passes = ctrl.passes;
+  out->graphed = graph ? 1 : 0;
+  return 0;
+}
+
 int kb_optimize(kb_handle* h, const kb_optimizer_options* opts, kb_solution* out) {
   if (!h || !opts || !out) return fail("kb_optimize: null");
   if (!h->uploaded) return fail("kb_optimize: no observations");
+  if (opts->policy == 2) return optimize_dogleg(h, opts, out);
   if (opts->policy != 0 && opts->policy != 1) return fail("kb_optimize: unknown policy");
   KB_HIP(hipSetDevice(h->device));
   const int max_passes = 2 * opts->max_iterations + 1;
@@ -1912,6 +2041,88 @@ int kb_optimize_marginal_analyze(kb_handle* h, const kb_optimizer_options* opts,
                                  kb_marginal_info* analyze_info, double* analyze_sv_out, double* analyze_V_out) {
   return optimize_marginal(h, opts, mopts, out, info, sv_out, V_out, true, analyze_info, analyze_sv_out,
                            analyze_V_out);
+}
+
+
+int kb_set_dogleg_options(kb_handle* h, const kb_dogleg_options* opts) {
+  if (!h) return fail("kb_set_dogleg_options: null");
+  const kb_dogleg_options def{0.0};
+  const kb_dogleg_options o = opts ? *opts : def;
+  if (!(o.delta_init >= 0.0) || !std::isfinite(o.delta_init))
+    return fail("kb_set_dogleg_options: delta_init must be finite and >= 0");
+  h->dl_opts = o;
+  return 0;
+}
+
+int kb_dogleg_step(kb_handle* h, double delta, double* dx_out, kb_dogleg_info* info, int* ok) {
+  if (!h || !ok) return fail("kb_dogleg_step: null");
+  if (!h->uploaded) return fail("kb_dogleg_step: no observations");
+  if (!h->sys_valid) return fail("kb_dogleg_step: no intact system (call kb_build first; the optimizer loops do "
+                                 "not leave the per-call blocks)");
+  if (sharded(h)) return fail("kb_dogleg_step: per-call quantity of an unsharded handle");
+  if (!(delta >= 0.0) || !std::isfinite(delta)) return fail("kb_dogleg_step: delta must be finite and >= 0");
+  KB_HIP(hipSetDevice(h->device));
+  unprepare(h);
+  if (ensure_dl(h, 0)) return -1;
+  const KbDlBuf b = h->dl;
+  KbDl st{};
+  st.delta = delta;
+  st.step_type = -1;
+  KB_HIP(hipMemcpyAsync(b.s, &st, sizeof(KbDl), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_dl_sd_frames, dim3((h->F + h->C + 3) / 4), dim3(256), 0, h->stream, h->d, b, 0);
+  hipLaunchKernelGGL(k_dl_sd_final, dim3(1), dim3(256), 0, h->stream, h->d, b, 0);
+  KB_HIP(hipGetLastError());
+  KB_HIP(hipMemcpyAsync(&st, b.s, sizeof(KbDl), hipMemcpyDeviceToHost, h->stream));
+  KB_HIP(hipStreamSynchronize(h->stream));
+  auto fill = [&](const KbDl& s, bool stepped) {
+    if (!info) return;
+    info->step_type = stepped ? s.step_type : -1;
+    info->delta = s.delta;
+    info->beta = s.beta;
+    info->sd_scale = s.sd_scale;
+    info->dx_sd_norm = s.dx_sd_norm;
+    info->dx_gn_norm = s.dx_gn_norm;
+    info->L0_over_J = stepped ? s.L0 / s.J : 0.0;
+  };
+  if (st.need_gn) {
+    // the GN step: lambda = 0, no conditioner, the direct factorisation, into the held-step buffer (as kb_solve)
+    DlScope sc(h, nullptr, b.dxgn);
+    h->d.host_lambda = 0.0;
+    h->d.cond2 = nullptr;
+    h->d.pcs_cb = nullptr;
+    const int one = 1;
+    KB_HIP(hipMemcpyAsync(&h->d.ctrl->solve_ok, &one, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (launch_schur(h, 0) || launch_colsum(h, 0) || launch_solve(h, 0, 0)) return -1;
+    int okd = 0;
+    KB_HIP(hipMemcpyAsync(&okd, &h->d.ctrl->solve_ok, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    KB_HIP(hipStreamSynchronize(h->stream));
+    if (!okd) {
+      *ok = 0;
+      fill(st, false);
+      return 0;
+    }
+    if (launch_backsub(h, 0, 0, 0)) return -1;
+  }
+  hipLaunchKernelGGL(k_dl_select, dim3(1), dim3(256), 0, h->stream, h->d, b, 0);
+  hipLaunchKernelGGL(k_dl_step, dim3(b.nstep), dim3(256), 0, h->stream, h->d, b, 0);
+  KB_HIP(hipGetLastError());
+  KB_HIP(hipMemcpyAsync(&st, b.s, sizeof(KbDl), hipMemcpyDeviceToHost, h->stream));
+  if (dx_out) KB_HIP(hipMemcpyAsync(dx_out, h->d.dx, sizeof(double) * h->ncols, hipMemcpyDeviceToHost, h->stream));
+  KB_HIP(hipStreamSynchronize(h->stream));
+  *ok = 1;
+  fill(st, true);
+  return 0;
+}
+
+int kb_get_dogleg_trace(kb_handle* h, double* out, int32_t cap) {
+  if (!h || !out) return fail("kb_get_dogleg_trace: null");
+  KB_HIP(hipSetDevice(h->device));
+  KbCtrl ctrl{};
+  KB_HIP(hipMemcpy(&ctrl, h->d.ctrl, sizeof(KbCtrl), hipMemcpyDeviceToHost));
+  if (ctrl.policy != 2 || !h->dl.trace) return 0;
+  const int n = std::min(cap, std::min(ctrl.n_trace, h->dl_trace_cap));
+  if (n > 0) KB_HIP(hipMemcpy(out, h->dl.trace, sizeof(double) * kDlTrace * n, hipMemcpyDeviceToHost));
+  return n;
 }
 
 int kb_get_trace(kb_handle* h, double* trace, int32_t cap) {

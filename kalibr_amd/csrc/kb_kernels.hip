@@ -5815,7 +5815,7 @@ __global__ void __launch_bounds__(256) k_rjr_final(KbDev d, const double* part, 
   if (tid == 0) out[0] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-__global__ void __launch_bounds__(256) k_cost(KbDev d, int which) {
+__device__ __forceinline__ void cost_views_block(const KbDev& d, int which) {
   KbCtrl* c = d.ctrl;
   __shared__ double part[4];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -5847,6 +5847,7 @@ __global__ void __launch_bounds__(256) k_cost(KbDev d, int which) {
   __syncthreads();
   if (threadIdx.x == 0) d.costpart[blockIdx.x] = ((part[0] + part[1]) + part[2]) + part[3];
 }
+__global__ void __launch_bounds__(256) k_cost(KbDev d, int which) { cost_views_block(d, which); }
 
 // fixed-order block reduction (one block of 256)
 __device__ double block_reduce(double s, double* sh, bool is_max) {
@@ -6010,7 +6011,7 @@ __global__ void k_pol_init(KbDev d, KbOpts o) {
 }
 
 // per-call update (kb_apply_update): all DVs from state[cur] -> state[1-cur]
-__global__ void __launch_bounds__(256) k_update_all(KbDev d) {
+__device__ __forceinline__ void update_all_thread(const KbDev& d) {
   KbCtrl* c = d.ctrl;
   const double* in = d.state + (size_t)c->cur * d.S;
   double* out = d.state + (size_t)(1 - c->cur) * d.S;
@@ -6023,6 +6024,7 @@ __global__ void __launch_bounds__(256) k_update_all(KbDev d) {
   if (t < N - 1) update_pose(in + d.off_base + 7 * t, d.dx + cam_arg(d.col_base, t), out + d.off_base + 7 * t);
   if (t < d.F) update_pose(in + d.off_frame + 7 * t, d.dx + d.C + 6 * t, out + d.off_frame + 7 * t);
 }
+__global__ void __launch_bounds__(256) k_update_all(KbDev d) { update_all_thread(d); }
 
 // f64 MFMA fragment-layout self test: D = A * B (16x16x16 in 4 k-steps) with asymmetric A and B;
 // lane l supplies A[l&15][k0 + (l>>4)] and B[k0 + (l>>4)][l&15]; D read back through the C/D map

@@ -701,6 +701,116 @@ bool GaussNewtonTrustRegionPolicy::solveSystemImplementation(double, bool, int n
   return _solver->solveSystem(outDx);
 }
 
+// ---------------------------------------------------------------- DogLeg (DogLegTrustRegionPolicy.cpp:11-161)
+namespace {
+double norm2(const std::vector<double>& v) {
+  double s = 0.0;
+  for (double x : v) s += x * x;
+  return s;
+}
+}  // namespace
+
+void DogLegTrustRegionPolicy::optimizationStartingImplementation(double) {
+  _dx_sd_norm = 0;
+  _dx_gn_norm = 0;
+  _L0 = 0;
+  _sd_scale = 0;
+  _beta = 0;
+  _stepType = None;
+  _delta = _deltaInit;  // deviation 1 (the reference: 0)
+  _p_delta = 0;
+  _gnHeld = false;
+}
+
+bool DogLegTrustRegionPolicy::solveSystemImplementation(double J, bool previousIterationFailed, int nThreads,
+                                                        std::vector<double>& outDx) {
+  if (!_solver) throw LinearSystemSolver::Exception("The solver is null");
+  // same check as in the LM lambda update
+  const double rho = get_dJ() / _L0;
+  if (!isFirstIteration()) {  // update trust region
+    _p_delta = _delta;
+    if (rho > 0.75) {  // step succeeded
+      const double dx_norm3 = 3 * std::sqrt(norm2(_dx));
+      if (!(_delta > dx_norm3)) _delta = dx_norm3;
+    } else if (rho > 0 && rho < 0.25) {  // step almost failed
+      _delta /= 2.0;
+    } else if (rho <= 0) {  // step failed: after a GN step the trust region becomes half the GN step
+      if (_stepType == GN)
+        _delta = _dx_gn_norm / 2.0;
+      else
+        _delta /= 2.0;
+    }
+  }
+  // successful step: rebuild the system and recalculate the steepest-descent solution
+  if (!previousIterationFailed) {
+    _solver->buildSystem(nThreads, true);
+    const std::vector<double>& g = _solver->rhs();
+    _sd_scale = norm2(g) / _solver->rhsJtJrhs();
+    _dx_sd.resize(g.size());
+    for (size_t i = 0; i < g.size(); ++i) _dx_sd[i] = _sd_scale * g[i];
+    _dx_sd_norm = std::sqrt(norm2(_dx_sd));
+    _gnHeld = false;  // invalidate the GN solution
+  }
+  if (_dx_sd_norm >= _delta && _delta != 0) {  // trust region smaller than SD: scale SD to fit into it
+    _dx.resize(_dx_sd.size());
+    for (size_t i = 0; i < _dx.size(); ++i) _dx[i] = _delta / _dx_sd_norm * _dx_sd[i];
+    _L0 = _delta * (2 * _dx_sd_norm - _delta) / (2 * _sd_scale);
+    _stepType = SD;
+  } else {
+    if (!_gnHeld) {
+      if (!_solver->solveSystem(_dx_gn)) return false;  // deviation 2: not held, retried on the next iteration
+      _gnHeld = true;
+      _dx_gn_norm = std::sqrt(norm2(_dx_gn));
+    }
+    const size_t n = _dx_sd.size();
+    if (_delta == 0) {  // the first step: |dx_sd + (dx_gn - dx_sd) / 2|
+      double s = 0.0;
+      for (size_t i = 0; i < n; ++i) {
+        const double v = _dx_sd[i] + 0.5 * (_dx_gn[i] - _dx_sd[i]);
+        s += v * v;
+      }
+      _delta = std::sqrt(s);
+    }
+    if (_dx_gn_norm <= _delta) {  // trust region larger than the GN step: take it
+      _dx = _dx_gn;
+      _L0 = J;
+      _stepType = GN;
+    } else {  // interpolate on the line between the Cauchy point and the GN step
+      double gdnsd_norm_sqr = 0.0, c = 0.0;
+      for (size_t i = 0; i < n; ++i) {
+        const double d = _dx_gn[i] - _dx_sd[i];
+        gdnsd_norm_sqr += d * d;
+        c += _dx_sd[i] * d;
+      }
+      if (c <= 0) {
+        _beta = -c + std::sqrt(c * c + gdnsd_norm_sqr * (_delta * _delta - _dx_sd_norm * _dx_sd_norm));
+        _beta /= gdnsd_norm_sqr;
+      } else {
+        _beta = (_delta * _delta - _dx_sd_norm * _dx_sd_norm);
+        _beta /= c + std::sqrt(c * c + gdnsd_norm_sqr * (_delta * _delta - _dx_sd_norm * _dx_sd_norm));
+      }
+      _dx.resize(n);
+      for (size_t i = 0; i < n; ++i) _dx[i] = _dx_sd[i] + _beta * (_dx_gn[i] - _dx_sd[i]);
+      // the reference's first term, 1/2 * _sd_scale * (1-_beta)^2 * |rhs|^2, carries the integer expression 1/2 = 0
+      // (:134): kept at 0
+      _L0 = _beta * (2 - _beta) * J;
+      _stepType = DL;
+    }
+  }
+  outDx = _dx;
+  return true;
+}
+
+const char* DogLegTrustRegionPolicy::stepTypeName() const {
+  return _stepType == SD ? "SD" : _stepType == GN ? "GN" : _stepType == DL ? "DL" : "";
+}
+
+std::ostream& DogLegTrustRegionPolicy::printState(std::ostream& out) const {
+  out << "DL - delta:" << _delta << ", " << stepTypeName();
+  if (_stepType == DL) out << ", beta:" << _beta;
+  return out;
+}
+
 // ---------------------------------------------------------------- Optimizer2 (Optimizer2.cpp:183-273)
 Optimizer2::Optimizer2(const Optimizer2Options& options) : _options(options) {}
 
@@ -809,8 +919,13 @@ SolutionReturnValue Optimizer2::optimizeOnDevice(int syncEvery) {
     o.lambda_init = lm->lambdaInit();
   } else if (std::dynamic_pointer_cast<GaussNewtonTrustRegionPolicy>(policy)) {
     o.policy = 1;
+  } else if (auto dl = std::dynamic_pointer_cast<DogLegTrustRegionPolicy>(policy)) {
+    o.policy = 2;
+    const kb_dogleg_options dlo{dl->deltaInit()};
+    if (kb_set_dogleg_options(static_cast<kb_handle*>(gpu->handle()), &dlo) < 0)
+      throw Exception(std::string("kb_set_dogleg_options: ") + kb_last_error());
   } else {
-    throw Exception("optimizeOnDevice: only the LM and GN policies run device-resident");
+    throw Exception("optimizeOnDevice: only the LM, GN and dog-leg policies run device-resident");
   }
   o.max_iterations = _options.maxIterations;
   o.convergence_dx = _options.convergenceDeltaX;
@@ -825,6 +940,13 @@ SolutionReturnValue Optimizer2::optimizeOnDevice(int syncEvery) {
   const int n = kb_get_trace(h, _trace.data(), cap);
   if (n < 0) throw Exception(std::string("kb_get_trace: ") + kb_last_error());
   _trace.resize(4 * (size_t)n);
+  _dlTrace.clear();
+  if (o.policy == 2) {
+    _dlTrace.assign(6 * (size_t)cap, 0.0);
+    const int m = kb_get_dogleg_trace(h, _dlTrace.data(), cap);
+    if (m < 0) throw Exception(std::string("kb_get_dogleg_trace: ") + kb_last_error());
+    _dlTrace.resize(6 * (size_t)m);
+  }
   SolutionReturnValue srv;
   srv.JStart = s.J_start;
   srv.JFinal = s.J_final;

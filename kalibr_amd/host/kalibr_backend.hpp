@@ -476,6 +476,40 @@ class GaussNewtonTrustRegionPolicy : public TrustRegionPolicy {
                                  std::vector<double>& outDx) override;
 };
 
+/// DogLegTrustRegionPolicy (aslam_backend/src/DogLegTrustRegionPolicy.cpp:11-161 and its header), statement by
+/// statement over any LinearSystemSolver (buildSystem, rhs, rhsJtJrhs, solveSystem).  Two deliberate deviations:
+///  1. Initial radius: the reference starts at delta = 0 (:19), so its first step is always DL with beta = 1/2;
+///     deltaInit (default 0: the reference) is what optimizationStarting assigns to delta.
+///  2. Failed linear solve: the reference sets gnComputed before it knows the solve succeeded (:60, :94-99) and reads
+///     a _dx_gn it never computed on the next iteration.  Here the GN step counts as held only after a completed
+///     solve; a failed one is retried on the next (again failed) iteration, and no step is applied.
+class DogLegTrustRegionPolicy : public TrustRegionPolicy {
+ public:
+  enum StepType { SD = 0, GN = 1, DL = 2, None = -1 };
+  explicit DogLegTrustRegionPolicy(double deltaInit = 0.0) : _deltaInit(deltaInit) {}
+  bool revertOnFailure() override { return true; }
+  std::ostream& printState(std::ostream& out) const override;
+  std::string name() const override { return "dog_leg"; }
+  bool requiresAugmentedDiagonal() const override { return false; }
+  double deltaInit() const { return _deltaInit; }
+  double delta() const { return _delta; }
+  double beta() const { return _beta; }
+  StepType stepType() const { return _stepType; }
+  const char* stepTypeName() const;
+
+ protected:
+  void optimizationStartingImplementation(double J) override;
+  bool solveSystemImplementation(double J, bool previousIterationFailed, int nThreads,
+                                 std::vector<double>& outDx) override;
+
+ private:
+  std::vector<double> _dx, _dx_sd, _dx_gn;
+  double _deltaInit;
+  double _dx_sd_norm = 0, _dx_gn_norm = 0, _L0 = 0, _sd_scale = 0, _beta = 0, _delta = 0, _p_delta = 0;
+  StepType _stepType = None;
+  bool _gnHeld = false;  // _dx_gn is the GN step of the built system (deviation 2)
+};
+
 // ---------------------------------------------------------------- optimizer
 struct Optimizer2Options {  // Optimizer2Options.hpp:9-42 (defaults kept)
   double convergenceDeltaJ = 1e-3;
@@ -494,8 +528,8 @@ class Optimizer2 {
   explicit Optimizer2(const Optimizer2Options& options);
   /// host-driven loop, Optimizer2.cpp:183-273 statement by statement (any LinearSystemSolver)
   SolutionReturnValue optimize();
-  /// the same loop device-resident (GpuLinearSystemSolver with an LM or GN policy): one captured graph per
-  /// pass, the host only polls the done flag every `syncEvery` passes
+  /// the same loop device-resident (GpuLinearSystemSolver with an LM, GN or dog-leg policy): captured graphs of
+  /// passes, the host only polls the done flag every `syncEvery` passes
   SolutionReturnValue optimizeOnDevice(int syncEvery = 0);
   /// Optimizer2::computeHessian (Optimizer2.cpp:389-402): evaluateError, setConstantConditioner(lambda), buildSystem,
   /// copyHessian -- the blocks with lambda^2 on the diagonal
@@ -509,13 +543,15 @@ class Optimizer2 {
   std::vector<std::vector<double>> computeCovarianceBlocks(const std::vector<std::pair<int, int>>& blockIndices,
                                                            double lambda);
   const Optimizer2Options& options() const { return _options; }
-  /// per-pass [J, lambda, deltaX, accepted] of the last optimizeOnDevice()
+  /// per-pass [J, lambda, deltaX, accepted] of the last optimizeOnDevice() (dog-leg: the lambda column is delta)
   const std::vector<double>& trace() const { return _trace; }
+  /// dog-leg policy: per-pass [delta, step type, beta, L0, |dx_sd|, |dx_gn|] of the last optimizeOnDevice()
+  const std::vector<double>& doglegTrace() const { return _dlTrace; }
 
  private:
   Optimizer2Options _options;
   std::vector<double> _dx;
-  std::vector<double> _trace;
+  std::vector<double> _trace, _dlTrace;
 };
 
 // ---------------------------------------------------------------- incremental estimator
