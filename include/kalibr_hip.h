@@ -63,7 +63,7 @@ const char* kb_last_error(void);
 /* Replaces LinearSystemSolver::initMatrixStructure (LinearSystemSolver.cpp:117-138) for
  * ReprojectionError terms: one term per observed corner, grouped in views.
  * Views must be sorted by frame (then camera); one view per (frame, camera).
- *   y            [n_corners][2]  measured keypoints (invR = I, CalibrationTools.hpp:391-393)
+ *   y            [n_corners][2]  measured keypoints (invR = I, CalibrationTools.hpp:391-393, unless kb_set_corner_invR)
  *   corner_id    [n_corners]     target corner index of each term
  *   view_offsets [n_views+1]     corner range of each view
  *   view_frame   [n_views], view_cam [n_views] */
@@ -80,12 +80,54 @@ int kb_state_size(const kb_handle* h);
 int kb_num_cols(const kb_handle* h);     /* JCols = C + 6F */
 int kb_camera_cols(const kb_handle* h);  /* C = sum(intrinsics) + 6(N-1) */
 
-/* LinearSystemSolver::evaluateError (LinearSystemSolver.cpp:81-92): chi^2 = sum e^T invR e. */
+/* LinearSystemSolver::evaluateError (LinearSystemSolver.cpp:81-92): chi^2 = sum e^T invR e; sum w(s) s on a weighted
+ * handle (kb_set_mestimator / kb_set_corner_invR below). */
 int kb_eval_cost(kb_handle* h, double* J_out);
 /* LinearSystemSolver::buildSystem (SparseCholeskyLinearSystemSolver.cpp:39-46): J, rhs = -J^T e,
- * assembled as the arrow normal equations (no explicit J).  use_mestimator must be 0 or 1
- * (Kalibr2 uses NoMEstimator, weight 1). */
+ * assembled as the arrow normal equations (no explicit J).  use_mestimator: 1 applies the M-estimator weights, 0 the
+ * corner invR only (Optimizer2::computeHessian); the same system on an unweighted handle (Kalibr2's default:
+ * NoMEstimator, invR = I). */
 int kb_build(kb_handle* h, int use_mestimator);
+
+/* Robust reprojection terms: ErrorTerm::setMEstimatorPolicy (aslam_backend/src/MEstimatorPolicies.cpp) and
+ * ErrorTermFs::setInvR (aslam_backend/include/aslam/backend/implementation/ErrorTerm.hpp:118-127) for every term of an
+ * unsharded camera handle.  A term has the raw squared error s = e^T invR e and the weight w = getWeight(s):
+ *   KB_MEST_HUBER(k)              s < k^2 ? 1 : k / sqrt(s)             (MEstimatorPolicies.cpp:64-66)
+ *   KB_MEST_CAUCHY(sigma^2)       1 / (1 + s / sigma^2)                 (:46-49)
+ *   KB_MEST_GEMAN_MCCLURE(sigma^2) sigma^2 / (sigma^2 + s)^2            (:31-34)
+ *   KB_MEST_BLAKE_ZISSERMAN(eps)  exp(-s) / (exp(-s) + eps)             (:104-106)
+ * Cost (ErrorTerm.cpp:20-24): kb_eval_cost and the costs inside kb_optimize return sum w(s) s, always weighted.
+ * Build (ErrorTerm.hpp(impl):170-192): the rows of a term are sqrt(w) sqrtInvR^T [J | e], so H = sum w J^T invR J and
+ * rhs = -sum w J^T invR e; kb_build(h, 0) applies invR only (Optimizer2::computeHessian, Optimizer2.cpp:398-400),
+ * kb_build(h, 1) and the device-resident loops both.  Only invR enters, not which square root: the Cholesky factor
+ * is used.  Deviation from the reference: it evaluates w at the squared error cached by the last evaluateError; the
+ * device evaluates w at the state it builds at (inside Optimizer2 the two coincide).
+ * A handle with an estimator != NONE or an invR set is "weighted": kb_eval_cost, kb_build, everything that reads the
+ * built blocks (kb_get_normal_blocks, kb_get_rhs, kb_rhs_jtj_rhs, kb_solve, kb_covariance), kb_apply_update /
+ * kb_revert and kb_optimize with the LM and GN policies (GN through the general, non-fused pass) work on it; sharding
+ * (kb_comm_init*), the marginal / incremental entry points, kb_append_frames / kb_drop_last_frames, the dog-leg
+ * policy / kb_dogleg_step and the fused GN entry points (kb_run_gn_iterations, kb_gn_prepare, kb_gn_launch) return an
+ * error until both settings are cleared.  An unweighted handle launches exactly the kernels it launched before. */
+enum kb_mestimator_kind {
+  KB_MEST_NONE = 0,
+  KB_MEST_HUBER = 1,
+  KB_MEST_CAUCHY = 2,
+  KB_MEST_GEMAN_MCCLURE = 3,
+  KB_MEST_BLAKE_ZISSERMAN = 4
+};
+typedef struct kb_mestimator {
+  int32_t kind; /* KB_MEST_* */
+  double param; /* k | sigma^2 | sigma^2 | epsilon; positive and finite */
+} kb_mestimator;
+/* m == NULL or kind NONE clears the estimator. */
+int kb_set_mestimator(kb_handle* h, const kb_mestimator* m);
+/* invR3: n symmetric 2x2 matrices as [a, b, c] = [[a, b], [b, c]], each positive definite (checked on the host).
+ * n == 0 or NULL clears; n == 1 one matrix for every corner; n == n_corners one per corner in upload order.
+ * The Cholesky factor (l00, l10, l11) of each matrix is stored on the device once. */
+int kb_set_corner_invR(kb_handle* h, const double* invR3, int32_t n);
+/* w and s of every term at the current state, upload order: w_out [n_corners], s_out [n_corners] or NULL. */
+int kb_get_mestimator_weights(kb_handle* h, double* w_out, double* s_out);
+
 /* LinearSystemSolver::setConstantConditioner (LinearSystemSolver.cpp:111-114):
  * "the square of this value will be added to the diagonal" (LinearSystemSolver.hpp:33-39). */
 int kb_set_constant_conditioner(kb_handle* h, double diag);

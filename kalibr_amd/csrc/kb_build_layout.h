@@ -1,0 +1,61 @@
+// Launch layout of the build kernels (k_build / k_buildp) as plain integer arithmetic: frames per block, threads
+// per block and dynamic LDS.  Host only and free of HIP, so the decisions that depend on it (does a rig fit, may a
+// handle switch between the two kernels) are testable without a device.
+#pragma once
+#include <cstddef>
+
+namespace kb_blay {
+
+constexpr int kXS = 17;            // kb_kernels.hip's XS (kb_capi.hip asserts that the two agree)
+constexpr int kTargetLds = 1536;   // kb_kernels.hip's kTargetLds
+constexpr size_t kLdsLimit = 160 * 1024;
+constexpr size_t kBuildpStaticLds = 4096;  // k_buildp's static LDS (control copies, tables, counters), an upper bound
+
+struct Rig {
+  int N;    // cameras
+  int C;    // camera-block columns
+  int K;    // target corners
+  int wpb;  // view waves per k_build block
+  int bpc;  // k_buildp blocks per CU
+};
+
+// frames per build block for F frames
+inline int gframes(bool pipe, int bpc, int F) { return pipe ? (F + 256 * bpc - 1) / (256 * bpc) : (F + 511) / 512; }
+
+// k_buildp's frame waves
+inline int frame_waves(int C) {
+  const int nbz = (C + 16) / 16;
+  return (nbz * (nbz + 1) / 2 + 1) / 2 <= 5 ? 2 : 4;
+}
+
+// threads per build block
+inline int build_threads(const Rig& r, bool pipe) { return 64 * (pipe ? r.N + frame_waves(r.C) : r.wpb); }
+
+// dynamic LDS (bytes) of the build kernel at `gf` frames per block (the staged frame poses); *tg: k_buildp stages
+// the target corners in LDS too
+inline size_t build_lds(const Rig& r, bool pipe, int gf, int* tg_out) {
+  const int N = r.N, C = r.C;
+  const int CZ = 16 * ((C + 16) / 16);  // [Y | z] row stride of the Schur tiles
+  const int tgl = (3 * r.K <= kTargetLds ? 3 * r.K : 0) + 8 * gf;
+  if (pipe) {  // k_buildp: tiles | H | chains G | view outputs | frame sums | frame-wave buffers | K | target,
+               // poses | the second view-output buffer
+    const int np = N * (N - 1) / 2;
+    const size_t vbs = 44 * N + 6 * CZ;  // view outputs dH | dg | intrinsic columns (+ the frame sums in place)
+    const size_t base = N * 64 * kXS + N * 256 + N * 36 + 2 * vbs + 40 + 6 * CZ + 36 * np + 8 * gf;
+    // the target corners are staged when they fit beside the rest
+    const bool tg = 3 * r.K <= kTargetLds && sizeof(double) * (base + 3 * r.K) + kBuildpStaticLds <= kLdsLimit;
+    if (tg_out) *tg_out = tg ? 1 : 0;
+    return sizeof(double) * (base + (tg ? 3 * r.K : 0));
+  }
+  if (tg_out) *tg_out = 0;
+  return sizeof(double) * (r.wpb * 64 * kXS + r.wpb * 256 + N * (256 + 256 + 64 + 36 + 36 + 8) + 36 + 16 * CZ +
+                           18 * N * (N - 1) + tgl);
+}
+
+// the build kernel's LDS fits at F frames.  k_build always stages a target of 3 K <= kTargetLds doubles, k_buildp
+// only when there is room: a rig that k_buildp takes can be too large for k_build (robust terms)
+inline bool build_fits(const Rig& r, bool pipe, int F) {
+  return build_lds(r, pipe, gframes(pipe, r.bpc, F), nullptr) + (pipe ? kBuildpStaticLds : 0) <= kLdsLimit;
+}
+
+}  // namespace kb_blay

@@ -31,6 +31,13 @@ const void* build_fn(int mb, bool pipe, bool wide) {
   return mb == 1 ? (const void*)k_build<1, GN, MM> : mb == 4 ? (const void*)k_build<4, GN, MM>
                                                              : (const void*)k_build<7, GN, MM>;
 }
+
+// weighted handles (robust terms, kb_robust.hip): always k_build, the general (non-fused) pass only
+const void* build_fn_w(int mb) {
+  using namespace kb;
+  return mb == 1 ? (const void*)k_build<1, false, MM, true> : mb == 4 ? (const void*)k_build<4, false, MM, true>
+                                                                      : (const void*)k_build<7, false, MM, true>;
+}
 }  // namespace
 
 #define KB_CAT2(a, b) a##b
@@ -38,3 +45,4 @@ const void* build_fn(int mb, bool pipe, bool wide) {
 const void* KB_CAT(kb_build_fn_, KB_TU_ID)(bool gn, int mb, bool pipe, bool wide) {
   return gn ? build_fn<true>(mb, pipe, wide) : build_fn<false>(mb, pipe, wide);
 }
+const void* KB_CAT(kb_build_fn_w_, KB_TU_ID)(int mb) { return build_fn_w(mb); }

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/kalibr_hip.h"
+#include "kb_build_layout.h"
 #include "kb_kernels.hip"
 #include "kb_pcg.hip"
 #include "kb_dogleg.hip"
@@ -134,6 +135,12 @@ struct kb_handle {
   bool xar_failed = false;        // a k_xar wait of this rank timed out (comm_check): agreed on at the next loop start
   double* xar_agree_buf = nullptr;  // [2]: this rank's failure flag | the sum over the ranks
   bool buildp_wide = false;  // k_buildp<.., MW = 8> (multi-model rigs with <= 8 waves per block)
+  // robust terms (kb_set_mestimator / kb_set_corner_invR): the settings themselves live in d.rb_*
+  bool build_pipe0 = false;  // build_pipe of the unweighted handle (a weighted one always takes k_build)
+  double* rb_L = nullptr;    // [NC][3] per-corner Cholesky factors of invR
+  size_t rb_L_n = 0;         // corners rb_L is sized for
+  double* rb_ws = nullptr;   // [2][NC] kb_get_mestimator_weights: w | s
+  size_t rb_ws_n = 0;
   double* rjr = nullptr;     // [F + 1] kb_rhs_jtj_rhs: per-frame terms | result
   double* cov_cc = nullptr;  // kb_covariance: Sigma_cc [C][C] | Sigma_ff [F][36] | Sigma_fc [F][6][C] (lazily allocated,
   double* cov_ff = nullptr;  // (re)sized for the current frame count like rjr)
@@ -216,7 +223,9 @@ struct kb_handle {
 // The build kernels of each camera-model set live in their own translation unit (kb_build_tu.hip, -DKB_TU_ID=id):
 // kb_build_fn_<id>(gn, mb, pipe, wide) returns the k_build / k_buildp instantiation (mb: Schur tiles per wave of
 // k_build 1 | 4 | 7, or per frame wave of k_buildp 5 | 7).
-#define KB_BUILD_TU_DECL(id) const void* kb_build_fn_##id(bool gn, int mb, bool pipe, bool wide);
+#define KB_BUILD_TU_DECL(id)                                            \
+  const void* kb_build_fn_##id(bool gn, int mb, bool pipe, bool wide); \
+  const void* kb_build_fn_w_##id(int mb);
 KB_BUILD_TU_DECL(0)
 KB_BUILD_TU_DECL(1)
 KB_BUILD_TU_DECL(2)
@@ -243,10 +252,38 @@ static const void* pick_build(int mb, unsigned mm, bool pipe, bool wide) {
   }
 }
 
-// frames per build block for F frames
-static int gframes_for(const kb_handle* h, int F) {
-  return h->build_pipe ? (F + 256 * h->bpc - 1) / (256 * h->bpc) : (F + 511) / 512;
+// The weighted build kernel k_build<mb, false, mm, WT = true> (robust terms) of the rig's camera-model set.
+static const void* pick_build_w(int mb, unsigned mm) {
+  switch (mm) {
+    case 1u << KB_PINHOLE_RADTAN: return kb_build_fn_w_0(mb);
+    case 1u << KB_OMNI_RADTAN: return kb_build_fn_w_1(mb);
+    case 1u << KB_EUCM: return kb_build_fn_w_2(mb);
+    case 1u << KB_OMNI: return kb_build_fn_w_3(mb);
+    case 1u << KB_DS: return kb_build_fn_w_4(mb);
+    case 1u << KB_PINHOLE_EQUI: return kb_build_fn_w_5(mb);
+    case 1u << KB_PINHOLE_FOV: return kb_build_fn_w_6(mb);
+    case (1u << KB_OMNI_RADTAN) | (1u << KB_EUCM): return kb_build_fn_w_7(mb);
+    default: return kb_build_fn_w_8(mb);
+  }
 }
+
+// a handle with an estimator != NONE or an invR set: the weighted kernel instantiations
+static bool weighted(const kb_handle* h) { return h->d.rb_kind != KB_MEST_NONE || h->d.rb_n != 0; }
+
+static const char* robust_refusal(const kb_handle* h, const char* what) {
+  static thread_local std::string m;
+  if (!weighted(h)) return nullptr;
+  m = std::string(what) + ": not available on a weighted handle (an M-estimator or a corner invR is set; clear them "
+      "with kb_set_mestimator(h, NULL) and kb_set_corner_invR(h, NULL, 0))";
+  return m.c_str();
+}
+#define KB_REFUSE_WEIGHTED(h, what)                            \
+  do {                                                         \
+    if (const char* m_ = robust_refusal(h, what)) return fail(m_); \
+  } while (0)
+
+// frames per build block for F frames
+static int gframes_for(const kb_handle* h, int F) { return kb_blay::gframes(h->build_pipe, h->bpc, F); }
 
 // the frame-count-dependent layout: columns, state size, build blocks (frames per block), step rows
 static void set_frame_counts(kb_handle* h) {
@@ -264,32 +301,17 @@ static void set_frame_counts(kb_handle* h) {
 // dynamic LDS of the build kernel at `gframes` frames per block (the staged frame poses); *tg: the target corners
 // are staged in LDS too.  k_buildp's static LDS (control copies, chain / intrinsic table, column info, counters) is
 // below this
-constexpr size_t kBuildpStaticLds = 4096;
-static size_t build_lds_for(const kb_handle* h, int gframes, int* tg_out) {
-  const int N = h->N, C = h->C, WPB = h->d.wpb;
-  const int CZ = 16 * ((C + 16) / 16);  // [Y | z] row stride of the Schur tiles
-  const int tgl = (3 * h->K <= kTargetLds ? 3 * h->K : 0) + 8 * gframes;
-  if (h->build_pipe) {  // k_buildp: tiles | H | chains G | view outputs | frame sums | frame-wave buffers | K | target,
-                        // poses | the second view-output buffer
-    const int np = N * (N - 1) / 2;
-    const size_t vbs = 44 * N + 6 * CZ;  // view outputs dH | dg | intrinsic columns (+ the frame sums in place)
-    const size_t base = N * 64 * XS + N * 256 + N * 36 + 2 * vbs + 40 + 6 * CZ + 36 * np + 8 * gframes;
-    // the target corners are staged when they fit beside the rest
-    const bool tg = 3 * h->K <= kTargetLds && sizeof(double) * (base + 3 * h->K) + kBuildpStaticLds <= 160 * 1024;
-    if (tg_out) *tg_out = tg ? 1 : 0;
-    return sizeof(double) * (base + (tg ? 3 * h->K : 0));
-  }
-  if (tg_out) *tg_out = 0;
-  return sizeof(double) * (WPB * 64 * XS + WPB * 256 + N * (256 + 256 + 64 + 36 + 36 + 8) + 36 + 16 * CZ +
-                           18 * N * (N - 1) + tgl);
-}
+// (the arithmetic is kb_build_layout.h's)
+using kb_blay::kBuildpStaticLds;
+static_assert(kb_blay::kXS == XS && kb_blay::kTargetLds == kTargetLds, "kb_build_layout.h: kernel constants");
+static kb_blay::Rig layout_rig(const kb_handle* h) { return {h->N, h->C, h->K, h->d.wpb, h->bpc}; }
 
-static size_t build_lds(kb_handle* h) { return build_lds_for(h, h->d.gframes, &h->d.bp_tg); }
+static size_t build_lds(kb_handle* h) {
+  return kb_blay::build_lds(layout_rig(h), h->build_pipe, h->d.gframes, &h->d.bp_tg);
+}
 
 // the build kernel's LDS fits at F frames (checked before kb_append_frames / kb_drop_last_frames change anything)
-static bool build_lds_fits(const kb_handle* h, int F) {
-  return build_lds_for(h, gframes_for(h, F), nullptr) + (h->build_pipe ? kBuildpStaticLds : 0) <= 160 * 1024;
-}
+static bool build_lds_fits(const kb_handle* h, int F) { return kb_blay::build_fits(layout_rig(h), h->build_pipe, F); }
 
 static void drop_graphs(kb_handle* h) {
   for (auto& g : h->graphs) {
@@ -407,6 +429,48 @@ static int relayout(kb_handle* h) {
   return 0;
 }
 
+// the build kernels of the handle: the Schur-tile bucket mb and the instantiations for its camera-model set (one-model
+// rigs and the omni-radtan + EUCM rig of configs[2] get their own build kernels; any other mix uses the all-models
+// instantiation).  A weighted handle (robust terms) takes k_build<mb, false, mm, true> for every pass.
+static void set_build_kernels(kb_handle* h) {
+  const KbDev& d = h->d;
+  const int nbz = (h->C + 16) / 16, ntiles = nbz * (nbz + 1) / 2;
+  const int tb = (ntiles + d.wpb - 1) / d.wpb;
+  h->mb = h->build_pipe ? ((ntiles + 1) / 2 <= 5 ? 5 : 7) : tb <= 1 ? 1 : tb <= 4 ? 4 : 7;
+  unsigned mm = 0;
+  for (int i = 0; i < h->N; ++i) mm |= 1u << d.model[i];
+  if (weighted(h)) {
+    h->fn_build = h->fn_build_gn = pick_build_w(h->mb, mm);
+    return;
+  }
+  h->fn_build = pick_build<false>(h->mb, mm, h->build_pipe, h->buildp_wide);
+  h->fn_build_gn = pick_build<true>(h->mb, mm, h->build_pipe, h->buildp_wide);
+}
+
+// A change of the robust settings: a weighted handle always builds with k_build (the layout KB_BUILD_PIPE=0 gives:
+// frames per block, block partial rows, threads, LDS), an unweighted one goes back to exactly what kb_create chose.
+// Captured graphs hold the old kernels and arguments.
+// The setters ask robust_fits before they change anything, so a refused setting leaves the handle as it was.
+static bool robust_fits(const kb_handle* h, bool weighted_after) {
+  return kb_blay::build_fits(layout_rig(h), h->build_pipe0 && !weighted_after, h->F);
+}
+
+static int robust_relayout(kb_handle* h) {
+  h->build_pipe = h->build_pipe0 && !weighted(h);
+  h->build_threads = kb_blay::build_threads(layout_rig(h), h->build_pipe);
+  set_build_kernels(h);
+  return relayout(h);
+}
+
+// a HIP error inside robust_relayout: the settings are restored by the caller, this puts kernel, threads and LDS
+// back in step with them (the first error message stays)
+static int robust_relayout_failed(kb_handle* h) {
+  const std::string e = g_err;
+  robust_relayout(h);
+  g_err = e;
+  return -1;
+}
+
 extern "C" {
 
 const char* kb_last_error(void) { return g_err.c_str(); }
@@ -486,6 +550,8 @@ kb_handle* kb_create(const kb_layout* L) {
   // KB_BUILD_PIPE=0 keeps k_build for comparison
   h->build_pipe = d.nsplit == 1 && h->N <= kBuildpMaxCams;
   if (const char* e = std::getenv("KB_BUILD_PIPE")) h->build_pipe = h->build_pipe && std::atoi(e) != 0;
+  h->build_pipe0 = h->build_pipe;
+  d.rb_l[0] = d.rb_l[2] = 1.0;  // no invR: the identity factor
   const int nbz0 = (h->C + 16) / 16, nf = (nbz0 * (nbz0 + 1) / 2 + 1) / 2 <= 5 ? 2 : 4;  // k_buildp frame waves
   h->build_threads = 64 * (h->build_pipe ? h->N + nf : d.wpb);
   if (h->build_pipe) {
@@ -613,15 +679,9 @@ kb_handle* kb_create(const kb_layout* L) {
   {
     // Schur-sum tiles per wave (template bucket): ceil(lower tiles of [Y|z]^T [Y|z] / waves)
     const int nbz = (h->C + 16) / 16, ntiles = nbz * (nbz + 1) / 2;
-    const int tb = (ntiles + d.wpb - 1) / d.wpb, ts = (ntiles + 3) / 4;
-    h->mb = h->build_pipe ? ((ntiles + 1) / 2 <= 5 ? 5 : 7) : tb <= 1 ? 1 : tb <= 4 ? 4 : 7;
+    const int ts = (ntiles + 3) / 4;
     h->ms = ts <= 1 ? 1 : ts <= 4 ? 4 : 7;
-    // camera-model set: one-model rigs (and the omni-radtan + EUCM rig of configs[2]) get their own build
-    // kernels; any other mix uses the all-models instantiation
-    unsigned mm = 0;
-    for (int i = 0; i < h->N; ++i) mm |= 1u << d.model[i];
-    h->fn_build = pick_build<false>(h->mb, mm, h->build_pipe, h->buildp_wide);
-    h->fn_build_gn = pick_build<true>(h->mb, mm, h->build_pipe, h->buildp_wide);
+    set_build_kernels(h);
     h->fn_schur = h->ms == 1 ? (const void*)k_schur<1> : h->ms == 4 ? (const void*)k_schur<4> : (const void*)k_schur<7>;
   }
   hipFuncSetAttribute(h->fn_build, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_build);
@@ -738,6 +798,7 @@ int kb_append_frames(kb_handle* h, int32_t n_frames, int32_t n_views, int32_t n_
                      const uint16_t* corner_id, const uint32_t* view_offsets, const uint32_t* view_frame,
                      const uint8_t* view_cam, const double* frame_poses) {
   if (!h) return fail("kb_append_frames: null handle");
+  KB_REFUSE_WEIGHTED(h, "kb_append_frames");
   if (!h->uploaded) return fail("kb_append_frames: no observations (kb_upload_observations first)");
   if (sharded(h)) return fail("kb_append_frames: not available on a sharded handle");
   const int nf = n_frames, nv = n_views, nc = n_corners;
@@ -860,6 +921,7 @@ int kb_append_frames(kb_handle* h, int32_t n_frames, int32_t n_views, int32_t n_
 
 int kb_drop_last_frames(kb_handle* h, int32_t n_frames) {
   if (!h) return fail("kb_drop_last_frames: null handle");
+  KB_REFUSE_WEIGHTED(h, "kb_drop_last_frames");
   if (!h->uploaded) return fail("kb_drop_last_frames: no observations");
   if (sharded(h)) return fail("kb_drop_last_frames: not available on a sharded handle");
   if (n_frames < 1 || n_frames >= h->F) return fail("kb_drop_last_frames: must keep at least one frame");
@@ -926,7 +988,10 @@ int kb_get_state_flat(kb_handle* h, double* state) {
 
 // ---------------------------------------------------------------- launch helpers
 static int launch_cost(kb_handle* h, int which) {
-  hipLaunchKernelGGL(k_cost, dim3(h->d.nblk_cost), dim3(256), 0, h->stream, h->d, which);
+  if (weighted(h))  // sum w(s) s
+    hipLaunchKernelGGL(k_cost_w, dim3(h->d.nblk_cost), dim3(256), 0, h->stream, h->d, which);
+  else
+    hipLaunchKernelGGL(k_cost, dim3(h->d.nblk_cost), dim3(256), 0, h->stream, h->d, which);
   hipLaunchKernelGGL(k_reduce_cost, dim3(1), dim3(256), 0, h->stream, h->d);
   KB_HIP(hipGetLastError());
   return 0;
@@ -995,11 +1060,20 @@ static int launch_colsum(kb_handle* h, int gate, bool finish = true) {
   return 0;
 }
 
-static int launch_build(kb_handle* h, int gate, int fuse) {
+// use_mestimator false (kb_build(h, 0)): the kernel gets a copy of the parameters with the estimator off, so the
+// rows carry invR only (ErrorTerm.hpp(impl):178-180)
+static int launch_build(kb_handle* h, int gate, int fuse, bool use_mestimator = true) {
   KbDev& d = h->d;
   // per-call path: camera chains first; in the loop k_solve (or the loop start) computed them
   if (!gate) hipLaunchKernelGGL(k_pre, dim3(1), dim3(256), 0, h->stream, d, 0);
-  void* args[] = {&d, &gate, &fuse};
+  KbDev d_invr;
+  void* dp = &d;
+  if (!use_mestimator && d.rb_kind != KB_MEST_NONE) {
+    d_invr = d;
+    d_invr.rb_kind = KB_MEST_NONE;
+    dp = &d_invr;
+  }
+  void* args[] = {dp, &gate, &fuse};
   KB_HIP(hipLaunchKernel(d.gn_fused ? h->fn_build_gn : h->fn_build, dim3(d.nblk), dim3(h->build_threads), args,
                          h->lds_build, h->stream));
   return 0;
@@ -1025,8 +1099,12 @@ static int launch_solve(kb_handle* h, int gate, int do_update, bool from_rows = 
 }
 
 static int launch_backsub(kb_handle* h, int gate, int do_update, int with_cost) {
-  hipLaunchKernelGGL(k_backsub, dim3((h->F + kBsFrames - 1) / kBsFrames), dim3(64 * kBsFrames), 0, h->stream, h->d, gate,
-                     do_update, with_cost);
+  if (weighted(h) && with_cost)  // the candidate cost is sum w(s) s
+    hipLaunchKernelGGL(k_backsub_w, dim3((h->F + kBsFrames - 1) / kBsFrames), dim3(64 * kBsFrames), 0, h->stream, h->d,
+                       gate, do_update, with_cost);
+  else
+    hipLaunchKernelGGL(k_backsub, dim3((h->F + kBsFrames - 1) / kBsFrames), dim3(64 * kBsFrames), 0, h->stream, h->d, gate,
+                       do_update, with_cost);
   KB_HIP(hipGetLastError());
   return 0;
 }
@@ -1047,16 +1125,112 @@ int kb_eval_cost(kb_handle* h, double* J_out) {
 int kb_build(kb_handle* h, int use_mestimator) {
   if (!h) return fail("kb_build: null");
   if (!h->uploaded) return fail("kb_build: no observations");
-  (void)use_mestimator;  // NoMEstimator: weight 1 either way (ErrorTerm.cpp:11)
   KB_HIP(hipSetDevice(h->device));
   unprepare(h);
   h->sys_valid = false;
-  if (launch_build(h, 0, 0)) return -1;
+  // use_mestimator == 0 (Optimizer2::computeHessian, Optimizer2.cpp:398-400): invR only, weight 1; an unweighted
+  // handle builds the same system either way
+  if (launch_build(h, 0, 0, use_mestimator != 0)) return -1;
   if (launch_colsum(h, 0)) return -1;
   hipLaunchKernelGGL(k_camexpand, dim3(1), dim3(256), h->lds_camexp, h->stream, h->d, 0);
   KB_HIP(hipGetLastError());
   KB_HIP(hipStreamSynchronize(h->stream));
   h->sys_valid = true;
+  return 0;
+}
+
+// ---------------------------------------------------------------- robust terms (kb_robust.hip)
+static int robust_settable(kb_handle* h, const char* what) {
+  if (!h) return fail(std::string(what) + ": null handle");
+  if (sharded(h)) return fail(std::string(what) + ": robust terms run on unsharded handles only");
+  return 0;
+}
+
+int kb_set_mestimator(kb_handle* h, const kb_mestimator* m) {
+  if (robust_settable(h, "kb_set_mestimator")) return -1;
+  const int kind = m ? m->kind : KB_MEST_NONE;
+  if (kind < KB_MEST_NONE || kind > KB_MEST_BLAKE_ZISSERMAN) return fail("kb_set_mestimator: unknown estimator kind");
+  if (kind != KB_MEST_NONE && !(std::isfinite(m->param) && m->param > 0.0))
+    return fail("kb_set_mestimator: the estimator parameter must be positive and finite");
+  const bool was = weighted(h), will = kind != KB_MEST_NONE || h->d.rb_n != 0;
+  if (was != will && !robust_fits(h, will))
+    return fail("kb_set_mestimator: the k_build LDS budget is exceeded for this rig");
+  KB_HIP(hipSetDevice(h->device));
+  const int kind0 = h->d.rb_kind;
+  const double p0 = h->d.rb_param;
+  h->d.rb_kind = kind;
+  h->d.rb_param = kind != KB_MEST_NONE ? m->param : 0.0;
+  drop_graphs(h);  // captured kernel arguments hold the old settings
+  unprepare(h);
+  h->sys_valid = false;
+  if (was != will && robust_relayout(h)) {
+    h->d.rb_kind = kind0;
+    h->d.rb_param = p0;
+    return robust_relayout_failed(h);
+  }
+  return 0;
+}
+
+int kb_set_corner_invR(kb_handle* h, const double* invR3, int32_t n) {
+  if (robust_settable(h, "kb_set_corner_invR")) return -1;
+  if (!invR3) n = 0;
+  if (n != 0 && !h->uploaded) return fail("kb_set_corner_invR: no observations");
+  if (n != 0 && n != 1 && n != h->NC) return fail("kb_set_corner_invR: n must be 0, 1 or the number of corners");
+  std::vector<double> L(3 * (size_t)std::max(n, 0));
+  for (int k = 0; k < n; ++k) {  // lower Cholesky factor of [[a, b], [b, c]]
+    const double a = invR3[3 * k], b = invR3[3 * k + 1], c = invR3[3 * k + 2];
+    const double l00 = std::sqrt(a), l10 = b / l00, r = c - l10 * l10;
+    if (!(std::isfinite(a) && std::isfinite(b) && std::isfinite(c) && a > 0.0 && r > 0.0 && std::isfinite(l10)))
+      return fail("kb_set_corner_invR: invR of corner " + std::to_string(k) + " is not positive definite");
+    L[3 * k] = l00;
+    L[3 * k + 1] = l10;
+    L[3 * k + 2] = std::sqrt(r);
+  }
+  const bool was = weighted(h), will = h->d.rb_kind != KB_MEST_NONE || n != 0;
+  if (was != will && !robust_fits(h, will))
+    return fail("kb_set_corner_invR: the k_build LDS budget is exceeded for this rig");
+  KB_HIP(hipSetDevice(h->device));
+  if (n > 1) {
+    if (h->rb_L_n < (size_t)n) {
+      if (regrow(h, &h->rb_L, 3 * (size_t)n, 0)) return -1;
+      h->rb_L_n = (size_t)n;
+    }
+    KB_HIP(hipMemcpyAsync(h->rb_L, L.data(), sizeof(double) * L.size(), hipMemcpyHostToDevice, h->stream));
+    KB_HIP(hipStreamSynchronize(h->stream));
+  }
+  const KbDev d0 = h->d;
+  h->d.rb_n = n;
+  h->d.rb_L = n > 1 ? h->rb_L : nullptr;
+  h->d.rb_l[0] = n == 1 ? L[0] : 1.0;
+  h->d.rb_l[1] = n == 1 ? L[1] : 0.0;
+  h->d.rb_l[2] = n == 1 ? L[2] : 1.0;
+  drop_graphs(h);
+  unprepare(h);
+  h->sys_valid = false;
+  if (was != will && robust_relayout(h)) {
+    h->d.rb_n = d0.rb_n;
+    h->d.rb_L = d0.rb_L;
+    for (int q = 0; q < 3; ++q) h->d.rb_l[q] = d0.rb_l[q];
+    return robust_relayout_failed(h);
+  }
+  return 0;
+}
+
+int kb_get_mestimator_weights(kb_handle* h, double* w_out, double* s_out) {
+  if (!h || !w_out) return fail("kb_get_mestimator_weights: null");
+  if (!h->uploaded) return fail("kb_get_mestimator_weights: no observations");
+  if (sharded(h)) return fail("kb_get_mestimator_weights: unsharded handles only");
+  KB_HIP(hipSetDevice(h->device));
+  const size_t n = (size_t)h->NC;
+  if (h->rb_ws_n < n) {
+    if (regrow(h, &h->rb_ws, 2 * n, 0)) return -1;
+    h->rb_ws_n = n;
+  }
+  hipLaunchKernelGGL(k_rw_weights, dim3((h->V + 3) / 4), dim3(256), 0, h->stream, h->d, h->rb_ws, h->rb_ws + n);
+  KB_HIP(hipGetLastError());
+  KB_HIP(hipMemcpyAsync(w_out, h->rb_ws, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+  if (s_out) KB_HIP(hipMemcpyAsync(s_out, h->rb_ws + n, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+  KB_HIP(hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -1372,6 +1546,7 @@ static int run_marginal(kb_handle* h, const kb_marginal_options* o, int write_dx
 int kb_solve_marginal(kb_handle* h, const kb_marginal_options* opts, double* dx_out, int* ok, kb_marginal_info* info,
                       double* sv_out, double* V_out) {
   if (!h || !opts || !ok) return fail("kb_solve_marginal: null");
+  KB_REFUSE_WEIGHTED(h, "kb_solve_marginal");
   KB_HIP(hipSetDevice(h->device));
   unprepare(h);
   const int one = 1;
@@ -1391,6 +1566,7 @@ int kb_solve_marginal(kb_handle* h, const kb_marginal_options* opts, double* dx_
 int kb_analyze_marginal(kb_handle* h, const kb_marginal_options* opts, kb_marginal_info* info, double* sv_out,
                         double* V_out) {
   if (!h || !opts) return fail("kb_analyze_marginal: null");
+  KB_REFUSE_WEIGHTED(h, "kb_analyze_marginal");
   KB_HIP(hipSetDevice(h->device));
   kb_marginal_options un = *opts;
   un.column_scaling = 0;
@@ -1573,7 +1749,8 @@ struct GnFusedScope {
   ~GnFusedScope() { h->d = saved; }
 };
 
-static bool gn_fused(const kb_handle* h, int policy) { return policy == 1 && h->gn_fuse; }
+// (a weighted handle runs its GN passes through the general pass: the fused kernels carry no weights)
+static bool gn_fused(const kb_handle* h, int policy) { return policy == 1 && h->gn_fuse && !weighted(h); }
 
 // ev0 / ev1 (optional): HIP events recorded around the build kernel (kb_build_kernel_stats)
 static int enqueue_marg_pass(kb_handle* h);
@@ -1857,6 +2034,7 @@ static int enqueue_dl_pass(kb_handle* h) {
 
 static int optimize_dogleg(kb_handle* h, const kb_optimizer_options* opts, kb_solution* out) {
   if (sharded(h)) return fail("kb_optimize: the dog-leg policy (2) runs on unsharded handles only");
+  KB_REFUSE_WEIGHTED(h, "kb_optimize: the dog-leg policy (2)");
   KB_HIP(hipSetDevice(h->device));
   const int max_passes = 2 * opts->max_iterations + 1;
   if (ensure_trace(h, max_passes + 1) || ensure_dl(h, max_passes + 1)) return -1;
@@ -1956,6 +2134,7 @@ static int optimize_marginal(kb_handle* h, const kb_optimizer_options* opts, con
                              kb_marginal_info* ainfo, double* asv_out, double* aV_out) {
   if (!h || !opts || !mopts || !out) return fail("kb_optimize_marginal: null");
   if (!h->uploaded) return fail("kb_optimize_marginal: no observations");
+  KB_REFUSE_WEIGHTED(h, "kb_optimize_marginal");
   if (opts->policy != 1) return fail("kb_optimize_marginal: the IncrementalEstimator's policy is Gauss-Newton (1)");
   if (h->C > kMargMaxC) return fail("kb_optimize_marginal: camera block C > 112 is not supported");
   if (sharded(h)) return fail("kb_optimize_marginal: not available on a sharded handle");
@@ -2056,6 +2235,7 @@ int kb_set_dogleg_options(kb_handle* h, const kb_dogleg_options* opts) {
 
 int kb_dogleg_step(kb_handle* h, double delta, double* dx_out, kb_dogleg_info* info, int* ok) {
   if (!h || !ok) return fail("kb_dogleg_step: null");
+  KB_REFUSE_WEIGHTED(h, "kb_dogleg_step");
   if (!h->uploaded) return fail("kb_dogleg_step: no observations");
   if (!h->sys_valid) return fail("kb_dogleg_step: no intact system (call kb_build first; the optimizer loops do "
                                  "not leave the per-call blocks)");
@@ -2156,6 +2336,7 @@ static int capture_gn(kb_handle* h, int passes, bool with_end, hipGraphExec_t* o
 }
 
 int kb_gn_prepare(kb_handle* h, int32_t n_iter) {
+  if (h) KB_REFUSE_WEIGHTED(h, "kb_gn_prepare");
   if (!h || n_iter < 0) return fail("kb_gn_prepare: bad args");
   if (!h->uploaded) return fail("kb_gn_prepare: no observations");
   KB_HIP(hipSetDevice(h->device));
@@ -2197,6 +2378,7 @@ int kb_gn_prepare(kb_handle* h, int32_t n_iter) {
 }
 
 int kb_gn_launch(kb_handle* h, int32_t n_iter, double* seconds) {
+  if (h) KB_REFUSE_WEIGHTED(h, "kb_gn_launch");
   if (!h || n_iter < 0) return fail("kb_gn_launch: bad args");
   if (h->gn_prepared != n_iter) return fail("kb_gn_launch: not prepared for this pass count (kb_gn_prepare)");
   h->gn_prepared = -1;
@@ -2244,6 +2426,7 @@ int kb_gn_launch(kb_handle* h, int32_t n_iter, double* seconds) {
 }
 
 int kb_run_gn_iterations(kb_handle* h, int32_t n_iter, double* seconds) {
+  if (h) KB_REFUSE_WEIGHTED(h, "kb_run_gn_iterations");
   if (kb_gn_prepare(h, n_iter) < 0) return -1;
   return kb_gn_launch(h, n_iter, seconds);
 }
@@ -2709,6 +2892,7 @@ int kb_xar_test(kb_handle* h, int32_t nranks, int32_t rank, const void* handles6
 
 int kb_comm_init(kb_handle* h, const void* uid, int32_t nranks, int32_t rank) {
   if (!h || !uid) return fail("kb_comm_init: null");
+  KB_REFUSE_WEIGHTED(h, "kb_comm_init");
   KB_HIP(hipSetDevice(h->device));
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail("kb_comm_init: bad rank / nranks");
   if (sharded(h)) return fail("kb_comm_init: communicator already initialised");
@@ -2732,6 +2916,7 @@ int kb_comm_init_local(kb_handle* const* hs, int32_t n) {
   for (int r = 0; r < n; ++r) {
     if (!hs[r]) return fail("kb_comm_init_local: null handle");
     if (sharded(hs[r])) return fail("kb_comm_init_local: handle already sharded");
+    KB_REFUSE_WEIGHTED(hs[r], "kb_comm_init_local");
     for (int q = 0; q < r; ++q)
       if (hs[q] == hs[r]) return fail("kb_comm_init_local: handle listed twice");
     if (hs[r]->N != hs[0]->N || hs[r]->C != hs[0]->C) return fail("kb_comm_init_local: handles of different rigs");

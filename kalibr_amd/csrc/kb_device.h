@@ -146,6 +146,13 @@ struct KbDev {
   int dbg_stop;   // diagnostic build only (KB_STAMPS): stop point of the timed kernel (-1: run to the end)
   int dbg_flags;  // diagnostic build only: bit 0 run the camera LDL^T twice (rolled)
   long long* dbg_ts;  // diagnostic build only: [128] s_memrealtime stamps: k_solve (KB_TS) | k_buildp (KB_TSB, +64)
+  // robust reprojection terms (kb_set_mestimator / kb_set_corner_invR, kb_robust.hip): read by the weighted kernel
+  // instantiations only (k_build<.., WT = true>, k_cost_w, k_backsub_w, k_rw_weights)
+  const double* rb_L;  // [NC][3] Cholesky factors (l00, l10, l11) of the per-corner invR (rb_n > 1), upload order
+  double rb_l[3];      // the factor of every corner when rb_n <= 1 (identity when no invR is set)
+  double rb_param;     // k | sigma^2 | sigma^2 | epsilon of the estimator
+  int rb_kind;         // KB_MEST_*; 0: weight 1
+  int rb_n;            // 0: no invR | 1: one matrix for every corner | NC: one per corner
 };
 
 #ifdef KB_STAMPS

@@ -879,12 +879,17 @@ __device__ __forceinline__ void frame_step(const KbDev& d, int f, bool store, in
   }
 }
 
+#include "kb_robust.hip"
+
 // ---------------------------------------------------------------------------------------------
 // k_build: one block = a group of frames; waves = N * nsplit, wave w -> camera w % N, corner split w / N.
 // ---------------------------------------------------------------------------------------------
 // GNF: Gauss-Newton fused variant (applies the previous solve's frame steps; no folded pass end)
 // MM: camera-model set of the rig (kMmAll = any model; a single-model set compiles one projection)
-template <int TW, bool GNF, unsigned MM>
+// WT: robust terms (kb_robust.hip): a lane scales the two rows of its corner by sqrt(w) L^T before the LDS tile, so
+//     the local Hessian is sum w [J | -e]^T invR [J | -e] and H[15][15] = sum w s; the per-corner factor (rb_n > 1)
+//     is loaded in the round of cid / y
+template <int TW, bool GNF, unsigned MM, bool WT = false>
 __global__ void __launch_bounds__(512) k_build(KbDev d, int gate, int fuse) {
   pass_stamp(d);
   KbCtrl* c = d.ctrl;
@@ -987,10 +992,18 @@ __global__ void __launch_bounds__(512) k_build(KbDev d, int gate, int fuse) {
   for (int q = 0; q < 7; ++q) fp0[q] = sf[d.off_frame + 7 * f0 + q];
   int cidn;
   double2 yn;
+  RbFac Ln = {1.0, 0.0, 1.0};
+  bool rb_pc = false;  // per-corner factors (wave-uniform)
+  if constexpr (WT) {
+    rb_pc = d.rb_n > 1;
+    Ln = rb_uniform(d);
+  }
   {
     const int k = min(fv.x + sp * 64 + lane, max(fv.y - 1, 0));
     cidn = d.cid[k];
     yn = d.y[k];
+    if constexpr (WT)
+      if (rb_pc) Ln = rb_load(d, k);
   }
   const double* Kc = cam_K(d, bs);
   for (int q = tid; q < 18 * N * (N - 1); q += nth) {
@@ -1065,6 +1078,8 @@ __global__ void __launch_bounds__(512) k_build(KbDev d, int gate, int fuse) {
       const int k = min(fv.x + sp * 64 + lane, max(fv.y - 1, 0));
       cidn = d.cid[k];
       yn = d.y[k];
+      if constexpr (WT)
+        if (rb_pc) Ln = rb_load(d, k);
     }
     v4d acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
     {
@@ -1073,10 +1088,13 @@ __global__ void __launch_bounds__(512) k_build(KbDev d, int gate, int fuse) {
         const int k = base + lane;
         const int cid = cidn;
         const double2 yv = yn;
+        const RbFac Lv = Ln;
         if (base + NS * 64 < o1) {  // software-pipelined: next chunk's corner ids and keypoints
           const int kn = min(k + NS * 64, o1 - 1);
           cidn = d.cid[kn];
           yn = d.y[kn];
+          if constexpr (WT)
+            if (rb_pc) Ln = rb_load(d, kn);
         }
         double xr[2][16];
 #pragma unroll
@@ -1105,6 +1123,16 @@ __global__ void __launch_bounds__(512) k_build(KbDev d, int gate, int fuse) {
 #pragma unroll
             for (int q = 0; q < 9; ++q) xr[r][6 + q] = (q < nin) ? -Ji[r * KB_MAX_INTR + q] : 0.0;
             xr[r][15] = -(r == 0 ? e0 : e1);  // column 15 carries -e: H[:,15] = rhs part, H[15][15] = chi^2
+          }
+          if constexpr (WT) {  // rows -> sqrt(w) L^T rows (ErrorTerm.hpp(impl):170-192); column 15 then gives w s
+            double s, w;
+            rb_term(d, Lv, e0, e1, s, w);
+            const double sw = sqrt(w), a00 = sw * Lv.l00, a10 = sw * Lv.l10, a11 = sw * Lv.l11;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+              xr[0][q] = a00 * xr[0][q] + a10 * xr[1][q];
+              xr[1][q] = a11 * xr[1][q];
+            }
           }
         }
         KB_STAMP(d, 27);
@@ -5614,7 +5642,9 @@ __global__ void __launch_bounds__(256) k_post(KbDev d, int policy) {
 }
 
 constexpr int kBsFrames = 4;  // k_backsub: frames (waves) per block
-__global__ void __launch_bounds__(64 * kBsFrames) k_backsub(KbDev d, int gate, int do_update, int with_cost) {
+// WT: the candidate cost is sum w(s) s (robust terms, kb_robust.hip); the per-corner factors travel with cid / y
+template <bool WT>
+__device__ __forceinline__ void backsub_block(const KbDev& d, int gate, int do_update, int with_cost) {
   KbCtrl* c = d.ctrl;
   __shared__ double tg[kTargetLds];
   __shared__ double cch[KB_MAX_CAMS][24];  // candidate chains L (12) | intrinsics (KB_MAX_INTR) of every camera
@@ -5719,10 +5749,18 @@ __global__ void __launch_bounds__(64 * kBsFrames) k_backsub(KbDev d, int gate, i
       }
       int cidn = 0;
       double2 yn = make_double2(0.0, 0.0);
+      RbFac Ln = {1.0, 0.0, 1.0};
+      bool rb_pc = false;
+      if constexpr (WT) {
+        rb_pc = d.rb_n > 1;
+        Ln = rb_uniform(d);
+      }
       if (cm < N) {
         const int k = min(k0 + lane, hi(cm) - 1);
         cidn = d.cid[k];
         yn = d.y[k];
+        if constexpr (WT)
+          if (rb_pc) Ln = rb_load(d, k);
       }
       int lastc = -1;
       double R[9], t[3];
@@ -5730,6 +5768,7 @@ __global__ void __launch_bounds__(64 * kBsFrames) k_backsub(KbDev d, int gate, i
         const int cc = cm, kk = k0, hc = hi(cm);
         const int cid = cidn;
         const double2 yv = yn;
+        const RbFac Lv = Ln;
         k0 += 64;
         while (cm < N && k0 >= hi(cm)) {
           ++cm;
@@ -5739,6 +5778,8 @@ __global__ void __launch_bounds__(64 * kBsFrames) k_backsub(KbDev d, int gate, i
           const int k = min(k0 + lane, hi(cm) - 1);
           cidn = d.cid[k];
           yn = d.y[k];
+          if constexpr (WT)
+            if (rb_pc) Ln = rb_load(d, k);
         }
         if (cc != lastc) {
           rt_mul(cch[cc], cch[cc] + 9, Ri, ti, R, t);  // T_cam_w = L_cam(candidate) T_f^-1
@@ -5752,7 +5793,10 @@ __global__ void __launch_bounds__(64 * kBsFrames) k_backsub(KbDev d, int gate, i
           double u0, u1;
           project(cam_arg(d.model, cc), cch[cc] + 12, p0, p1, p2, u0, u1);
           const double e0 = yv.x - u0, e1 = yv.y - u1;
-          cost += e0 * e0 + e1 * e1;
+          if constexpr (WT)
+            cost += rb_cost(d, Lv, e0, e1);
+          else
+            cost += e0 * e0 + e1 * e1;
         }
       }
       cost = wave_sum_d(cost);
@@ -5770,6 +5814,13 @@ __global__ void __launch_bounds__(64 * kBsFrames) k_backsub(KbDev d, int gate, i
     }
     reinterpret_cast<double4*>(d.bpart)[f] = make_double4(cost, a1, a2, a3);
   }
+}
+__global__ void __launch_bounds__(64 * kBsFrames) k_backsub(KbDev d, int gate, int do_update, int with_cost) {
+  backsub_block<false>(d, gate, do_update, with_cost);
+}
+// weighted handles: the candidate cost is sum w(s) s
+__global__ void __launch_bounds__(64 * kBsFrames) k_backsub_w(KbDev d, int gate, int do_update, int with_cost) {
+  backsub_block<true>(d, gate, do_update, with_cost);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -5815,6 +5866,7 @@ __global__ void __launch_bounds__(256) k_rjr_final(KbDev d, const double* part, 
   if (tid == 0) out[0] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
+template <bool WT = false>
 __device__ __forceinline__ void cost_views_block(const KbDev& d, int which) {
   KbCtrl* c = d.ctrl;
   __shared__ double part[4];
@@ -5839,7 +5891,10 @@ __device__ __forceinline__ void cost_views_block(const KbDev& d, int which) {
       project(model, intr, p0, p1, p2, u, w);
       const double2 yv = d.y[k];
       const double e0 = yv.x - u, e1 = yv.y - w;
-      acc += e0 * e0 + e1 * e1;
+      if constexpr (WT)
+        acc += rb_cost(d, d.rb_n > 1 ? rb_load(d, k) : rb_uniform(d), e0, e1);
+      else
+        acc += e0 * e0 + e1 * e1;
     }
     acc = wave_sum_d(acc);
   }
@@ -5848,6 +5903,41 @@ __device__ __forceinline__ void cost_views_block(const KbDev& d, int which) {
   if (threadIdx.x == 0) d.costpart[blockIdx.x] = ((part[0] + part[1]) + part[2]) + part[3];
 }
 __global__ void __launch_bounds__(256) k_cost(KbDev d, int which) { cost_views_block(d, which); }
+// weighted handles: sum w(s) s (ErrorTerm.cpp:20-24)
+__global__ void __launch_bounds__(256) k_cost_w(KbDev d, int which) { cost_views_block<true>(d, which); }
+
+// ---------------------------------------------------------------------------------------------
+// k_rw_weights: one wave per view on the accepted state; s = e^T invR e and w(s) of every term in upload order
+// (kb_get_mestimator_weights): each lane writes its own corners, no reduction
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_rw_weights(KbDev d, double* w_out, double* s_out) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int v = blockIdx.x * 4 + wave;
+  if (v >= d.V) return;
+  const double* s = d.state + (size_t)d.ctrl->cur * d.S;
+  const int f = d.view_frame[v], cam = d.view_cam[v];
+  double R[9], t[3];
+  cam_from_state(d, s, cam, s + d.off_frame + 7 * f, R, t);
+  const int model = cam_arg(d.model, cam);
+  const double* intr = s + cam * KB_MAX_INTR;
+  const int o0 = d.view_off[v], o1 = d.view_off[v + 1];
+  const bool pc = d.rb_n > 1;
+  for (int k = o0 + lane; k < o1; k += 64) {
+    const int cid = d.cid[k];
+    const double2 yv = d.y[k];
+    const RbFac L = pc ? rb_load(d, k) : rb_uniform(d);
+    const double X0 = d.target[3 * cid], X1 = d.target[3 * cid + 1], X2 = d.target[3 * cid + 2];
+    const double p0 = R[0] * X0 + R[1] * X1 + R[2] * X2 + t[0];
+    const double p1 = R[3] * X0 + R[4] * X1 + R[5] * X2 + t[1];
+    const double p2 = R[6] * X0 + R[7] * X1 + R[8] * X2 + t[2];
+    double u, w;
+    project(model, intr, p0, p1, p2, u, w);
+    double sq, wt;
+    rb_term(d, L, yv.x - u, yv.y - w, sq, wt);
+    w_out[k] = wt;
+    s_out[k] = sq;
+  }
+}
 
 // fixed-order block reduction (one block of 256)
 __device__ double block_reduce(double s, double* sh, bool is_max) {

@@ -510,6 +510,15 @@ CalibrateCamerasResult calibrateCameras(const std::vector<int32_t>& models,
                                         std::shared_ptr<backend::MarginalLinearSystemSolver> estimatorSolver) {
   const size_t N = models.size();
   if (N < 2 || byCam.size() != N) throw std::runtime_error("calibrateCameras: at least two cameras, one list each");
+  // robust settings are checked before anything runs: a solver that cannot take them fails here, never at the end of
+  // a finished calibration
+  if (!(opt.cornerUncertainty > 0.0) || !std::isfinite(opt.cornerUncertainty))
+    throw std::invalid_argument("calibrateCameras: cornerUncertainty must be positive and finite");
+  if (opt.cornerUncertainty != 1.0 || (opt.mEstimator && opt.mEstimator->kind() != 0)) {
+    auto probe = stages.solver ? stages.solver() : nullptr;
+    if (!probe || !probe->supportsRobustTerms())
+      throw std::invalid_argument("calibrateCameras: cornerUncertainty / mEstimator need a stage solver with robust terms");
+  }
   CalibrateCamerasResult res;
   std::vector<CameraCalibrator> cams(N);
   for (size_t i = 0; i < N; ++i) cams[i] = CameraCalibrator{models[i], std::vector<double>(KB_MAX_INTR, 0.0)};
@@ -659,7 +668,10 @@ CalibrateCamerasResult calibrateCameras(const std::vector<int32_t>& models,
     try {
       auto sv = stages.solver();
       if (sv && sv->supportsCovariance()) {
-        sv->initMatrixStructure(est.getProblem(), false);
+        backend::CalibrationProblem fp = est.getProblem();  // the final batch problem, with the robust settings
+        if (opt.cornerUncertainty != 1.0) fp.cornerUncertainty(opt.cornerUncertainty);
+        if (opt.mEstimator) fp.setMEstimatorPolicy(opt.mEstimator);
+        sv->initMatrixStructure(fp, false);
         sv->setConstantConditioner(0.0);
         sv->buildSystem(16, false);
         const std::vector<int> dims = backend::canonicalBlockDimensions(models, 0);  // the camera DVs

@@ -146,6 +146,17 @@ struct CalibrateCamerasOptions {
   std::optional<size_t> maxBatches;                 // --max-batches
   size_t estimatorMaxIterations = 20;               // optimizer_options.maxIterations (:271)
   bool verbose = false;
+  /// corner_uncertainty (kalibr2/CalibrationTools.hpp:391-393): invR = I / sigma^2 of every reprojection term of the
+  /// final batch problem; 1.0 (the default) sets nothing.  parameterStdDev scales with it.
+  double cornerUncertainty = 1.0;
+  /// ErrorTerm::setMEstimatorPolicy for every term of the final batch problem (null: none).
+  /// NOTE: today this changes NO result of calibrateCameras.  The stages and the incremental estimator run unweighted
+  /// (their device paths carry no weights), and the only consumer of the final batch problem is the covariance, which
+  /// is Optimizer2::computeHessian's system (useMEstimator = false) and so ignores the estimator.  Passing Huber here
+  /// does not make the calibration resist outliers; its one effect is that a stage solver without robust terms is
+  /// refused up front.  The option is the hook for a batch refinement over the final problem; until that exists, use
+  /// CalibrationProblem::setMEstimatorPolicy with Optimizer2 over GpuLinearSystemSolver for a robust fit.
+  std::shared_ptr<const backend::MEstimator> mEstimator;
 };
 
 struct CalibrateCamerasResult {
@@ -171,7 +182,8 @@ struct CalibrateCamerasResult {
   /// how well determined the calibration is: sqrt of the diagonal of Sigma_cc = the camera block of (J^T J)^-1
   /// (lambda = 0) of the accepted batches' problem at the final state, camera columns in canonical order
   /// [intrinsics | baselines].  Filled only when the stage solver supportsCovariance() and the factorisation succeeds;
-  /// empty otherwise (never an error).
+  /// empty otherwise (never an error).  In units of options.cornerUncertainty (sigma px per corner): sigma times
+  /// the sigma = 1 values.
   std::vector<double> parameterStdDev;
 };
 

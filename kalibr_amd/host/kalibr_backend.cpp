@@ -5,11 +5,49 @@
 #include <chrono>
 #include <cmath>
 #include <iostream>
+#include <sstream>
 
 #include "kalibr_hip.h"
 
 namespace kalibr_amd {
 namespace backend {
+
+// ---------------------------------------------------------------- M-estimators (MEstimatorPolicies.cpp)
+int NoMEstimator::kind() const { return KB_MEST_NONE; }
+int GemanMcClureMEstimator::kind() const { return KB_MEST_GEMAN_MCCLURE; }
+int CauchyMEstimator::kind() const { return KB_MEST_CAUCHY; }
+int HuberMEstimator::kind() const { return KB_MEST_HUBER; }
+int BlakeZissermanMEstimator::kind() const { return KB_MEST_BLAKE_ZISSERMAN; }
+
+std::string GemanMcClureMEstimator::name() const {  // :35-39
+  std::stringstream ss;
+  ss << "Geman McClure (" << _sigma2 << ")";
+  return ss.str();
+}
+std::string CauchyMEstimator::name() const {  // :50-54
+  std::stringstream ss;
+  ss << "Cauchy (" << _sigma2 << ")";
+  return ss.str();
+}
+std::string HuberMEstimator::name() const {  // :67-71
+  std::stringstream ss;
+  ss << "Huber(" << _k << ")";
+  return ss.str();
+}
+BlakeZissermanMEstimator::BlakeZissermanMEstimator(size_t df, double pCut, double wCut)
+    : _df(df), _pCut(pCut), _wCut(wCut), _epsilon(computeEpsilon(df, pCut, wCut)) {}
+std::string BlakeZissermanMEstimator::name() const {  // :107-111
+  std::stringstream ss;
+  ss << "Blake-Zisserman(" << _epsilon << ")";
+  return ss.str();
+}
+double BlakeZissermanMEstimator::chi2InvCDF(double p, size_t df) const {  // :112-115 (boost's quantile there)
+  if (df != 2) throw std::invalid_argument("BlakeZissermanMEstimator: only df = 2 (closed-form chi-squared quantile)");
+  return -2.0 * std::log(1.0 - p);
+}
+double BlakeZissermanMEstimator::computeEpsilon(size_t df, double pCut, double wCut) const {  // :116-119
+  return (1 - wCut) / wCut * std::exp(-chi2InvCDF(pCut, df));
+}
 
 // ---------------------------------------------------------------- LinearSystemSolver defaults
 void LinearSystemSolver::setConditioner(const std::vector<double>& diag) {
@@ -429,6 +467,39 @@ void GpuLinearSystemSolver::initMatrixStructure(const CalibrationProblem& p, boo
   _conditioner = 0.0;
   _built = false;
   _rhs_valid = false;
+  _nCorners = (size_t)p.n_corners();
+  if (p.mEstimator) setMEstimatorPolicy(p.mEstimator);
+  if (!p.cornerInvR.empty()) setCornerInvR(p.cornerInvR);
+}
+
+void GpuLinearSystemSolver::setMEstimatorPolicy(std::shared_ptr<const MEstimator> m) {
+  if (!_h) throw Exception("setMEstimatorPolicy: initMatrixStructure first");
+  if (!m || m->kind() == KB_MEST_NONE) {
+    check(kb_set_mestimator(static_cast<kb_handle*>(_h), nullptr), "kb_set_mestimator");
+  } else {
+    const kb_mestimator km{(int32_t)m->kind(), m->parameter()};
+    check(kb_set_mestimator(static_cast<kb_handle*>(_h), &km), "kb_set_mestimator");
+  }
+  _built = false;
+  _rhs_valid = false;
+}
+
+void GpuLinearSystemSolver::setCornerInvR(const std::vector<double>& invR3) {
+  if (!_h) throw Exception("setCornerInvR: initMatrixStructure first");
+  if (invR3.size() % 3 != 0) throw Exception("setCornerInvR: three values [a, b, c] per matrix");
+  check(kb_set_corner_invR(static_cast<kb_handle*>(_h), invR3.empty() ? nullptr : invR3.data(), (int32_t)(invR3.size() / 3)),
+        "kb_set_corner_invR");
+  _built = false;
+  _rhs_valid = false;
+}
+
+std::vector<double> GpuLinearSystemSolver::mEstimatorWeights(std::vector<double>* squaredErrors) {
+  if (!_h) throw Exception("mEstimatorWeights: initMatrixStructure first");
+  std::vector<double> w(_nCorners);
+  if (squaredErrors) squaredErrors->assign(_nCorners, 0.0);
+  check(kb_get_mestimator_weights(static_cast<kb_handle*>(_h), w.data(), squaredErrors ? squaredErrors->data() : nullptr),
+        "kb_get_mestimator_weights");
+  return w;
 }
 
 double GpuLinearSystemSolver::evaluateError(size_t, bool) {
@@ -575,6 +646,7 @@ bool GpuLinearSystemSolver::appendFrames(const CalibrationProblem& p, size_t f0)
   check(kb_set_state_flat(h, p.state.data()), "kb_set_state_flat");
   _F = (size_t)p.n_frames;
   _N = (size_t)p.n_cams();
+  _nCorners = (size_t)p.n_corners();
   _JRows = 2 * (size_t)p.n_corners();
   _JCols = (size_t)kb_num_cols(h);
   _rhs.assign(_JCols, 0.0);
@@ -1003,6 +1075,8 @@ GpuMarginalLinearSolver::GpuMarginalLinearSolver(const LinearSolverOptions& o, c
 }
 
 void GpuMarginalLinearSolver::initMatrixStructure(const CalibrationProblem& p, bool useDiagonalConditioner) {
+  // the marginal / incremental device paths carry no weights: refused here, not at the first solve
+  if (p.weighted()) throw Exception(name() + ": this solver takes no M-estimator / corner invR");
   _analyzed = false;  // a changed system voids the fused analyzeMarginal result
   _g.initMatrixStructure(p, useDiagonalConditioner);
   _JRows = _g.JRows();

@@ -20,6 +20,7 @@
 #pragma once
 
 #include <cfloat>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <memory>
@@ -32,6 +33,85 @@
 
 namespace kalibr_amd {
 namespace backend {
+
+// ---------------------------------------------------------------- M-estimators
+// aslam::backend::MEstimator and its policies (aslam_backend/include/aslam/backend/MEstimatorPolicies.hpp,
+// src/MEstimatorPolicies.cpp): getWeight(squaredError) and name() as the reference's.  kind() / parameter() are what
+// the device takes (kb_set_mestimator).
+class MEstimator {
+ public:
+  virtual ~MEstimator() = default;
+  virtual double getWeight(double squaredError) const = 0;
+  virtual std::string name() const = 0;
+  virtual int kind() const = 0;          // kb_mestimator_kind
+  virtual double parameter() const = 0;  // k | sigma^2 | sigma^2 | epsilon
+};
+
+class NoMEstimator : public MEstimator {  // MEstimatorPolicies.cpp:17-22
+ public:
+  double getWeight(double) const override { return 1.0; }
+  std::string name() const override { return "none"; }
+  int kind() const override;
+  double parameter() const override { return 0.0; }
+};
+
+class GemanMcClureMEstimator : public MEstimator {  // :24-40
+ public:
+  explicit GemanMcClureMEstimator(double sigma2) : _sigma2(sigma2) {}
+  double getWeight(double error) const override {
+    const double se = _sigma2 + error;
+    return _sigma2 / (se * se);
+  }
+  std::string name() const override;
+  int kind() const override;
+  double parameter() const override { return _sigma2; }
+
+ private:
+  double _sigma2;
+};
+
+class CauchyMEstimator : public MEstimator {  // :42-55
+ public:
+  explicit CauchyMEstimator(double sigma2) : _sigma2(sigma2) {}
+  double getWeight(double error) const override { return 1.0 / (1.0 + error / _sigma2); }
+  std::string name() const override;
+  int kind() const override;
+  double parameter() const override { return _sigma2; }
+
+ private:
+  double _sigma2;
+};
+
+class HuberMEstimator : public MEstimator {  // :59-72
+ public:
+  explicit HuberMEstimator(double k) : _k(k), _k2(k * k) {}
+  double getWeight(double error) const override { return error < _k2 ? 1.0 : _k / std::sqrt(error); }
+  std::string name() const override;
+  int kind() const override;
+  double parameter() const override { return _k; }
+
+ private:
+  double _k, _k2;
+};
+
+class BlakeZissermanMEstimator : public MEstimator {  // :74-120
+ public:
+  /// df = 2 only (one reprojection term): chi2^-1(p, 2) = -2 ln(1 - p) in closed form; other df throw
+  /// std::invalid_argument (the reference takes the quantile from boost)
+  BlakeZissermanMEstimator(size_t df, double pCut = 0.999, double wCut = 0.1);
+  double getWeight(double mahalanobis2) const override {
+    return std::exp(-mahalanobis2) / (std::exp(-mahalanobis2) + _epsilon);
+  }
+  std::string name() const override;
+  int kind() const override;
+  double parameter() const override { return _epsilon; }
+  double chi2InvCDF(double p, size_t df) const;
+  double computeEpsilon(size_t df, double pCut, double wCut) const;
+
+ private:
+  size_t _df;
+  double _pCut, _wCut, _epsilon;
+};
 
 // ---------------------------------------------------------------- problem description
 // What CalibrateMultiCameraRig / CreateBatchProblem hand to the optimizer (CalibrationTools.hpp:376-521):
@@ -47,6 +127,21 @@ struct CalibrationProblem {
   std::vector<double> y;             // [n_corners][2]
   std::vector<double> state;         // flat design-variable values
   int n_frames = 0;
+  /// robust terms (ErrorTerm::setMEstimatorPolicy, ErrorTermFs::setInvR for every term): null = NoMEstimator;
+  /// cornerInvR empty = I, 3 values [a, b, c] = one symmetric 2x2 [[a, b], [b, c]] for every corner, 3 n_corners = one
+  /// per corner in term order.  GpuLinearSystemSolver takes them; GpuMarginalLinearSolver throws in
+  /// initMatrixStructure.  Nothing enforces this for other solvers: one whose supportsRobustTerms() is false has to
+  /// check weighted() in its own initMatrixStructure (callers such as calibrateCameras ask supportsRobustTerms first).
+  std::shared_ptr<const MEstimator> mEstimator;
+  std::vector<double> cornerInvR;
+  void setMEstimatorPolicy(std::shared_ptr<const MEstimator> m) { mEstimator = std::move(m); }
+  void clearMEstimatorPolicy() { mEstimator.reset(); }
+  void setCornerInvR(double a, double b, double c) { cornerInvR = {a, b, c}; }
+  void setCornerInvR(std::vector<double> invR3) { cornerInvR = std::move(invR3); }
+  void clearCornerInvR() { cornerInvR.clear(); }
+  /// corner_uncertainty (kalibr2/CalibrationTools.hpp:391-393): invR = I / sigma^2 for every corner
+  void cornerUncertainty(double sigma) { setCornerInvR(1.0 / (sigma * sigma), 0.0, 1.0 / (sigma * sigma)); }
+  bool weighted() const { return (mEstimator && mEstimator->kind() != 0) || !cornerInvR.empty(); }
   int n_cams() const { return (int)cam_model.size(); }
   int n_views() const { return (int)view_frame.size(); }
   int n_corners() const { return (int)corner_id.size(); }
@@ -142,6 +237,19 @@ class ProblemLinearSystemSolver : public LinearSystemSolver {
   /// state: [n, mean_u, mean_v, std_u, std_v, rmse] (sample std; rmse = |sum e| / sqrt(n), as the reference prints it)
   virtual std::vector<std::array<double, 6>> reprojectionErrorStatistics() {
     throw Exception(name() + ": no reprojection-error statistics");
+  }
+  /// robust terms: true when the solver takes an M-estimator and corner invR (the setters below; a weighted
+  /// CalibrationProblem in initMatrixStructure).  The defaults throw: a solver that cannot take weights never silently
+  /// drops them.
+  virtual bool supportsRobustTerms() const { return false; }
+  virtual void setMEstimatorPolicy(std::shared_ptr<const MEstimator>) { throw Exception(name() + ": no M-estimators"); }
+  virtual void clearMEstimatorPolicy() { setMEstimatorPolicy(nullptr); }
+  /// empty: I; 3 values: one matrix for every corner; 3 n_corners: one per corner
+  virtual void setCornerInvR(const std::vector<double>&) { throw Exception(name() + ": no corner invR"); }
+  /// w (and s = e^T invR e) of every term at the current state, term order
+  virtual std::vector<double> mEstimatorWeights(std::vector<double>* squaredErrors = nullptr) {
+    (void)squaredErrors;
+    throw Exception(name() + ": no M-estimator weights");
   }
 };
 
@@ -289,6 +397,13 @@ class GpuLinearSystemSolver : public ProblemLinearSystemSolver {
   std::vector<int> blockDimensions() const override { return canonicalBlockDimensions(_models, (int)_F); }
 
   std::vector<double> state() const override;
+  /// ErrorTerm::setMEstimatorPolicy / ErrorTermFs::setInvR for every term (kb_set_mestimator, kb_set_corner_invR); a
+  /// weighted CalibrationProblem sets both in initMatrixStructure.  buildSystem honours useMEstimator (false: invR
+  /// only, Optimizer2::computeHessian); evaluateError is always weighted (ErrorTerm.cpp:20-24)
+  bool supportsRobustTerms() const override { return true; }
+  void setMEstimatorPolicy(std::shared_ptr<const MEstimator> m) override;
+  void setCornerInvR(const std::vector<double>& invR3) override;
+  std::vector<double> mEstimatorWeights(std::vector<double>* squaredErrors = nullptr) override;
   std::vector<std::array<double, 6>> reprojectionErrorStatistics() override;  // kb_reprojection_error_stats
   void setState(const std::vector<double>& s);
   size_t cameraCols() const { return _C; }
@@ -308,6 +423,7 @@ class GpuLinearSystemSolver : public ProblemLinearSystemSolver {
   void* _h = nullptr;
   GpuOptions _opt;
   size_t _C = 0, _F = 0, _N = 0;
+  size_t _nCorners = 0;
   std::vector<int32_t> _models;
   double _conditioner = 0.0;
   bool _built = false;
