@@ -21,6 +21,7 @@
 //   TrustRegionPolicy.cpp:39-57, LevenbergMarquardtTrustRegionPolicy.cpp:50-113,
 //   GaussNewtonTrustRegionPolicy.cpp:18-39.
 #include "kb_device.h"
+#include "kb_syrk_tile.h"
 
 namespace kb {
 
@@ -85,6 +86,16 @@ __device__ __forceinline__ double dpp_d(double v) {
   const unsigned long long b = __double_as_longlong(v);
   const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffull), CTRL, 0xf, 0xf, false);
   const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, false);
+  return __longlong_as_double(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+
+// 64-bit DPP row rotation (CTRL = 0x120 + n: row_ror:n, lane i <- lane (i - n) & 15 of its 16-lane row).  Every lane
+// has a source, so bound_ctrl lets the compiler drop the "old" operand (no v_mov of 0 per half).
+template <int CTRL>
+__device__ __forceinline__ double rot_d(double v) {
+  const unsigned long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffull), CTRL, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, true);
   return __longlong_as_double(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
 
@@ -1725,7 +1736,13 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
           // rows n .. 63 of a partial pass are zero: only the groups of 4 k-steps (16 rows) holding valid rows are
           // issued (k-step ks = rows 4ks .. 4ks + 3, even ks into acc0, odd into acc1), the next group's operands in
           // flight during the current group's MFMAs (one LDS round trip per group, not per MFMA).  Row = lane: the
-          // lanes of a write hit distinct LDS bank pairs at the 17-double row stride.
+          // lanes of a write hit distinct LDS bank pairs at the 17-double row stride (KB_SYRK_DPP: by columns,
+          // kb_syrk_tile.h).
+#if defined(KB_SYRK_DPP) && !defined(KB_SYRK16)
+#define KB_TROW(q) kb_tile::store_idx(lane, q)  // by columns: conflict-free for the stores and for the two operand reads
+#else
+#define KB_TROW(q) (lane * XS + (q))
+#endif
 #ifdef KB_SYRK16
           const int ng = (min(64, o1 - base) + 15) >> 4;
 #else
@@ -1736,18 +1753,60 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
 #if defined(KB_CORNER_NOZERO) || defined(KB_CORNER_CLAMP)
             if (valid) {
 #pragma unroll
-              for (int q = 0; q < 16; ++q) Xw[lane * XS + q] = r ? xv[q] : xu[q];
+              for (int q = 0; q < 16; ++q) Xw[KB_TROW(q)] = r ? xv[q] : xu[q];
             } else {
 #pragma unroll
-              for (int q = 0; q < 16; ++q) Xw[lane * XS + q] = 0.0;
+              for (int q = 0; q < 16; ++q) Xw[KB_TROW(q)] = 0.0;
             }
 #else
             (void)valid;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) Xw[lane * XS + q] = r ? xv[q] : xu[q];
+            for (int q = 0; q < 16; ++q) Xw[KB_TROW(q)] = r ? xv[q] : xu[q];
 #endif
             KB_WAVE_SYNC();
-#ifndef KB_SYRK16
+#if defined(KB_SYRK_DPP) && !defined(KB_SYRK16)
+            {
+              // KB_SYRK_DPP (measured, not the default: DESIGN.md 3c, round 11): of the six operands per pair of row
+              // quads (below) only the two diagonal ones q0, q1 are read from LDS, from the tile stored by columns
+              // (kb_syrk_tile.h: conflict-free, 2 LDS cycles each).  A 16-lane DPP row holds one tile row, so the
+              // others are lane rotations within it: column (mcol + 4) & 15 is lane + 4 (row_ror:12 delivers lane
+              // (i + 4) & 15 to lane i, tools/micro/dpp_row_ror.hip), and the (0,2), (1,3) operand that a lane does
+              // not hold itself sits 8 lanes away, on the other side of the b < 2 split: one select before one
+              // row_ror:8 serves both sides.  The same values in the same order as the six reads (bitwise equal sums).
+              const bool lo = ((lane >> 2) & 3) < 2;
+              double xr[2][2];  // q0, q1 of two pairs (the next pair's loads in flight during this pair's MFMAs)
+              // pair p's reads sit 8 p doubles after pair 0's (immediate offsets).  q1 gets an address register of its
+              // own: off one register the compiler pairs the two reads into a ds_read2_b64, which the LDS serves in
+              // 16-lane groups over 32 banks, 2-way on this tile and 16 cycles against 2 + 2
+              const int x0o = kb_tile::read_idx(0, 0, lane);
+              int x1o = kb_tile::read_idx(0, 1, lane);
+              asm volatile("" : "+v"(x1o));
+              auto ld = [&](double* x, int pp) {
+                x[0] = Xw[x0o + 8 * pp];
+                x[1] = Xw[x1o + 8 * pp];
+                __builtin_amdgcn_sched_barrier(0);
+              };
+              auto mf = [&](const double* x) {
+                const double q0 = x[0], q1 = x[1];
+                const double e0 = rot_d<0x12C>(q0), e1 = rot_d<0x12C>(q1);
+                const double w = rot_d<0x128>(lo ? q1 : q0);
+                const double xa = lo ? q0 : w, xb = lo ? w : q1;
+                accD = __builtin_amdgcn_mfma_f64_4x4x4f64(q0, q0, accD, 0, 0, 0);
+                accO1 = __builtin_amdgcn_mfma_f64_4x4x4f64(q0, e0, accO1, 0, 0, 0);
+                accD = __builtin_amdgcn_mfma_f64_4x4x4f64(q1, q1, accD, 0, 0, 0);
+                accO1 = __builtin_amdgcn_mfma_f64_4x4x4f64(q1, e1, accO1, 0, 0, 0);
+                accO2 = __builtin_amdgcn_mfma_f64_4x4x4f64(xa, xb, accO2, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+              };
+              ld(xr[0], 0);
+#pragma unroll
+              for (int pp = 0; pp < 8; ++pp) {
+                if (pp >= np) break;  // wave-uniform
+                if (pp + 1 < 8) ld(xr[(pp + 1) & 1], pp + 1);  // unconditional: see the six-read form
+                mf(xr[pp & 1]);
+              }
+            }
+#elif !defined(KB_SYRK16)
             {
               // per pair of row quads (rows 8p .. 8p + 7): the diagonal-block operand of each quad (row mrow, column
               // mcol: the 16x16x4 operand), the (b, b+1) operand of each (column (mcol + 4) & 15), and the A / B
@@ -1785,7 +1844,12 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
 #pragma unroll
               for (int pp = 0; pp < 8; ++pp) {
                 if (pp >= np) break;  // wave-uniform
-                if (pp + 1 < np) ld(xr[(pp + 1) & 1], pp + 1);
+                // the next pair's loads are issued whether or not that pair holds valid rows (its operands are then
+                // not used; the rows are in the tile).  Behind `pp + 1 < np` the loads sat in a block of their own,
+                // and at the join the compiler no longer knew how many were in flight: it drained them all
+                // (s_waitcnt lgkmcnt(0..3)) before this pair's MFMAs, one exposed LDS round trip per pair.  In
+                // straight line it waits for this pair's operands only (lgkmcnt(7), (6), (4) in the six-read form).
+                if (pp + 1 < 8) ld(xr[(pp + 1) & 1], pp + 1);
                 mf(xr[pp & 1]);
               }
 #endif
