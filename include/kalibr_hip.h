@@ -107,7 +107,9 @@ int kb_build(kb_handle* h, int use_mestimator);
  * kb_revert and kb_optimize with the LM and GN policies (GN through the general, non-fused pass) work on it; sharding
  * (kb_comm_init*), the marginal / incremental entry points, kb_append_frames / kb_drop_last_frames, the dog-leg
  * policy / kb_dogleg_step and the fused GN entry points (kb_run_gn_iterations, kb_gn_prepare, kb_gn_launch) return an
- * error until both settings are cleared.  An unweighted handle launches exactly the kernels it launched before. */
+ * error until both settings are cleared.  An unweighted handle launches exactly the kernels it launched before.
+ * kb_set_robust_build (below) opts a handle into the weighted k_buildp, which brings the fused GN pass and its entry
+ * points back on a weighted handle. */
 enum kb_mestimator_kind {
   KB_MEST_NONE = 0,
   KB_MEST_HUBER = 1,
@@ -125,6 +127,18 @@ int kb_set_mestimator(kb_handle* h, const kb_mestimator* m);
  * n == 0 or NULL clears; n == 1 one matrix for every corner; n == n_corners one per corner in upload order.
  * The Cholesky factor (l00, l10, l11) of each matrix is stored on the device once. */
 int kb_set_corner_invR(kb_handle* h, const double* invR3, int32_t n);
+/* The build kernel of the handle while it is weighted.
+ *   KB_ROBUST_BUILD_GENERAL (default)  k_build<.., WT> for every pass, GN through the general pass (as above).
+ *   KB_ROBUST_BUILD_PIPE               the weighted k_buildp: kb_create's layout (frames per block, partial rows,
+ *     threads, LDS) is kept, kb_build_kernel_name says k_buildp, and GN passes are fused again: kb_optimize with the
+ *     GN policy, kb_run_gn_iterations, kb_gn_prepare and kb_gn_launch work (loop starts and the last step's cost stay
+ *     weighted: k_cost_w / k_backsub_w).  Everything else that a weighted handle refuses stays refused.  Accepted only
+ *     on an unsharded handle that kb_create gave k_buildp (4..8 cameras); otherwise an error naming the reason, the
+ *     handle as it was.
+ * The mode may be set before or after the estimator / invR and survives clearing them; an unweighted handle is not
+ * affected by it. */
+enum kb_robust_build { KB_ROBUST_BUILD_GENERAL = 0, KB_ROBUST_BUILD_PIPE = 1 };
+int kb_set_robust_build(kb_handle* h, int32_t mode);
 /* w and s of every term at the current state, upload order: w_out [n_corners], s_out [n_corners] or NULL. */
 int kb_get_mestimator_weights(kb_handle* h, double* w_out, double* s_out);
 

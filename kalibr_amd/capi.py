@@ -29,7 +29,7 @@ EXPORTS = [
     "kb_build_kernel_name", "kb_comm_get_unique_id", "kb_gn_pass_times", "kb_append_frames", "kb_drop_last_frames", "kb_optimize_marginal", "kb_optimize_marginal_analyze",
     "kb_comm_init", "kb_comm_init_local", "kb_comm_direct", "kb_xar_export", "kb_xar_test", "kb_selftest_mfma", "kb_solve_marginal", "kb_analyze_marginal",
     # robust terms (kb_set_corner_invR is in EXPORTS_MIXED_CASE below)
-    "kb_set_mestimator", "kb_get_mestimator_weights",
+    "kb_set_mestimator", "kb_get_mestimator_weights", "kb_set_robust_build",
     # block-Jacobi PCG (LinearSolverPCG)
     "kb_set_linear_solver", "kb_pcg_init", "kb_get_pcg_info",
     # configs[4]: B-spline pose trajectory + IMU
@@ -102,6 +102,7 @@ class MEstimator(C.Structure):
 POLICIES = {"lm": 0, "gn": 1, "dogleg": 2}
 # kb_mestimator_kind; the parameter is k | sigma^2 | sigma^2 | epsilon
 MESTIMATORS = {"none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3, "blake_zisserman": 4}
+ROBUST_BUILDS = {"general": 0, "pipe": 1}  # enum kb_robust_build
 
 
 def blake_zisserman_epsilon(df, p_cut, w_cut):
@@ -151,6 +152,7 @@ def lib():
         L.kb_set_mestimator.argtypes = [C.c_void_p, C.POINTER(MEstimator)]
         L.kb_set_corner_invR.argtypes = [C.c_void_p, dp, C.c_int32]
         L.kb_get_mestimator_weights.argtypes = [C.c_void_p, dp, dp]
+        L.kb_set_robust_build.argtypes = [C.c_void_p, C.c_int32]
         L.kb_set_constant_conditioner.argtypes = [C.c_void_p, C.c_double]
         L.kb_set_conditioner.argtypes = [C.c_void_p, dp]
         L.kb_solve.argtypes = [C.c_void_p, dp, C.POINTER(C.c_int)]
@@ -306,6 +308,11 @@ class Solver:
             return
         a = np.ascontiguousarray(invR3, dtype=np.float64).reshape(-1, 3)
         _check(lib().kb_set_corner_invR(self.h, _d(a), a.shape[0]))
+
+    def set_robust_build(self, mode="general"):
+        """The build kernel of the handle while it is weighted: "general" (k_build, GN through the general pass) or
+        "pipe" (the weighted k_buildp: kb_create's layout, fused GN passes; rigs that build with k_buildp only)."""
+        _check(lib().kb_set_robust_build(self.h, ROBUST_BUILDS[mode]))
 
     def mestimator_weights(self):
         """(w, s) of every term at the current state, upload order."""

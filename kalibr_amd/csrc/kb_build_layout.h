@@ -58,4 +58,15 @@ inline bool build_fits(const Rig& r, bool pipe, int F) {
   return build_lds(r, pipe, gframes(pipe, r.bpc, F), nullptr) + (pipe ? kBuildpStaticLds : 0) <= kLdsLimit;
 }
 
+// Robust terms (kb_set_mestimator / kb_set_corner_invR / kb_set_robust_build): the kernel a handle builds with.
+// `pipe0` is kb_create's choice for the unweighted handle; a weighted handle keeps it only in pipe mode
+// (KB_ROBUST_BUILD_PIPE: the weighted k_buildp), otherwise it builds with k_build.
+inline bool robust_pipe(bool pipe0, bool pipe_mode, bool weighted) { return pipe0 && (!weighted || pipe_mode); }
+
+// the build kernel of the handle in that robust state fits at F frames.  In pipe mode becoming weighted does not
+// change the layout, so a rig that kb_create accepted is never refused
+inline bool robust_fits(const Rig& r, bool pipe0, bool pipe_mode, bool weighted, int F) {
+  return build_fits(r, robust_pipe(pipe0, pipe_mode, weighted), F);
+}
+
 }  // namespace kb_blay

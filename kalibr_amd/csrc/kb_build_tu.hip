@@ -1,6 +1,6 @@
 // kb_build_tu.hip -- the build kernels (k_build / k_buildp) of ONE camera-model set, in a translation unit of their
 // own: the library compiles the nine model sets in parallel instead of instantiating ~100 large kernels in kb_capi.hip.
-// Compiled with -DKB_TU_ID=<0..8>; kb_capi.hip's pick_build dispatches to kb_build_fn_<id>.  kb_kernels.hip is
+// Compiled with -DKB_TU_ID=<0..8>; kb_capi.hip's pick_build* dispatch to kb_build_fn[_w|_pw]_<id>.  kb_kernels.hip is
 // included inside an unnamed namespace, so the non-template kernels it also defines stay internal to this TU (the
 // copies nothing here references are not emitted twice into one symbol).
 #include <hip/hip_runtime.h>
@@ -32,12 +32,32 @@ const void* build_fn(int mb, bool pipe, bool wide) {
                                                              : (const void*)k_build<7, GN, MM>;
 }
 
-// weighted handles (robust terms, kb_robust.hip): always k_build, the general (non-fused) pass only
+// weighted handles (robust terms, kb_robust.hip) in KB_ROBUST_BUILD_GENERAL mode: k_build, the general (non-fused) pass only
 const void* build_fn_w(int mb) {
   using namespace kb;
   return mb == 1 ? (const void*)k_build<1, false, MM, true> : mb == 4 ? (const void*)k_build<4, false, MM, true>
                                                                       : (const void*)k_build<7, false, MM, true>;
 }
+
+// weighted handles in KB_ROBUST_BUILD_PIPE mode: k_buildp<.., WT = true>, the general and the fused GN pass.  The
+// diagnostic / timing variants of k_buildp carry no weights (null: kb_set_robust_build refuses the mode)
+#if defined(KB_CORNER_OLD) || defined(KB_SYRK16) || defined(KB_CORNER_CLAMP) || defined(KB_CORNER_NOZERO) || \
+    defined(KB_DIAG_NOPROJ) || defined(KB_DIAG_NOSYRK)
+template <bool GN>
+const void* build_fn_pw(int, bool) {
+  return nullptr;
+}
+#else
+template <bool GN>
+const void* build_fn_pw(int mb, bool wide) {
+  using namespace kb;
+  constexpr int MWN = kBuildpMaxCams + 4;
+  if constexpr (__builtin_popcount(MM) >= 2) {
+    if (wide) return mb == 5 ? (const void*)k_buildp<5, GN, MM, 8, true> : (const void*)k_buildp<7, GN, MM, 8, true>;
+  }
+  return mb == 5 ? (const void*)k_buildp<5, GN, MM, MWN, true> : (const void*)k_buildp<7, GN, MM, MWN, true>;
+}
+#endif
 }  // namespace
 
 #define KB_CAT2(a, b) a##b
@@ -46,3 +66,6 @@ const void* KB_CAT(kb_build_fn_, KB_TU_ID)(bool gn, int mb, bool pipe, bool wide
   return gn ? build_fn<true>(mb, pipe, wide) : build_fn<false>(mb, pipe, wide);
 }
 const void* KB_CAT(kb_build_fn_w_, KB_TU_ID)(int mb) { return build_fn_w(mb); }
+const void* KB_CAT(kb_build_fn_pw_, KB_TU_ID)(bool gn, int mb, bool wide) {
+  return gn ? build_fn_pw<true>(mb, wide) : build_fn_pw<false>(mb, wide);
+}

@@ -136,7 +136,8 @@ struct kb_handle {
   double* xar_agree_buf = nullptr;  // [2]: this rank's failure flag | the sum over the ranks
   bool buildp_wide = false;  // k_buildp<.., MW = 8> (multi-model rigs with <= 8 waves per block)
   // robust terms (kb_set_mestimator / kb_set_corner_invR): the settings themselves live in d.rb_*
-  bool build_pipe0 = false;  // build_pipe of the unweighted handle (a weighted one always takes k_build)
+  bool build_pipe0 = false;  // build_pipe of the unweighted handle (a weighted one takes k_build unless rb_build is PIPE)
+  int rb_build = KB_ROBUST_BUILD_GENERAL;  // kb_set_robust_build: the build kernel of the weighted handle
   double* rb_L = nullptr;    // [NC][3] per-corner Cholesky factors of invR
   size_t rb_L_n = 0;         // corners rb_L is sized for
   double* rb_ws = nullptr;   // [2][NC] kb_get_mestimator_weights: w | s
@@ -225,7 +226,8 @@ struct kb_handle {
 // k_build 1 | 4 | 7, or per frame wave of k_buildp 5 | 7).
 #define KB_BUILD_TU_DECL(id)                                            \
   const void* kb_build_fn_##id(bool gn, int mb, bool pipe, bool wide); \
-  const void* kb_build_fn_w_##id(int mb);
+  const void* kb_build_fn_w_##id(int mb);                              \
+  const void* kb_build_fn_pw_##id(bool gn, int mb, bool wide);
 KB_BUILD_TU_DECL(0)
 KB_BUILD_TU_DECL(1)
 KB_BUILD_TU_DECL(2)
@@ -267,6 +269,23 @@ static const void* pick_build_w(int mb, unsigned mm) {
   }
 }
 
+// The weighted pipelined build kernel k_buildp<mb, GN, mm, MW, WT = true> (robust terms, KB_ROBUST_BUILD_PIPE); null
+// in a measurement variant of the library whose k_buildp carries no weights.
+template <bool GN>
+static const void* pick_build_pw(int mb, unsigned mm, bool wide) {
+  switch (mm) {
+    case 1u << KB_PINHOLE_RADTAN: return kb_build_fn_pw_0(GN, mb, wide);
+    case 1u << KB_OMNI_RADTAN: return kb_build_fn_pw_1(GN, mb, wide);
+    case 1u << KB_EUCM: return kb_build_fn_pw_2(GN, mb, wide);
+    case 1u << KB_OMNI: return kb_build_fn_pw_3(GN, mb, wide);
+    case 1u << KB_DS: return kb_build_fn_pw_4(GN, mb, wide);
+    case 1u << KB_PINHOLE_EQUI: return kb_build_fn_pw_5(GN, mb, wide);
+    case 1u << KB_PINHOLE_FOV: return kb_build_fn_pw_6(GN, mb, wide);
+    case (1u << KB_OMNI_RADTAN) | (1u << KB_EUCM): return kb_build_fn_pw_7(GN, mb, wide);
+    default: return kb_build_fn_pw_8(GN, mb, wide);
+  }
+}
+
 // a handle with an estimator != NONE or an invR set: the weighted kernel instantiations
 static bool weighted(const kb_handle* h) { return h->d.rb_kind != KB_MEST_NONE || h->d.rb_n != 0; }
 
@@ -280,6 +299,11 @@ static const char* robust_refusal(const kb_handle* h, const char* what) {
 #define KB_REFUSE_WEIGHTED(h, what)                            \
   do {                                                         \
     if (const char* m_ = robust_refusal(h, what)) return fail(m_); \
+  } while (0)
+// the fused GN entry points: a weighted handle has them in KB_ROBUST_BUILD_PIPE mode (the weighted k_buildp)
+#define KB_REFUSE_WEIGHTED_GN(h, what)                                                  \
+  do {                                                                                  \
+    if (!((h)->build_pipe && (h)->rb_build == KB_ROBUST_BUILD_PIPE)) KB_REFUSE_WEIGHTED(h, what); \
   } while (0)
 
 // frames per build block for F frames
@@ -431,7 +455,8 @@ static int relayout(kb_handle* h) {
 
 // the build kernels of the handle: the Schur-tile bucket mb and the instantiations for its camera-model set (one-model
 // rigs and the omni-radtan + EUCM rig of configs[2] get their own build kernels; any other mix uses the all-models
-// instantiation).  A weighted handle (robust terms) takes k_build<mb, false, mm, true> for every pass.
+// instantiation).  A weighted handle (robust terms) takes k_build<mb, false, mm, true> for every pass, or in
+// KB_ROBUST_BUILD_PIPE mode the weighted k_buildp pair (general pass | fused GN pass).
 static void set_build_kernels(kb_handle* h) {
   const KbDev& d = h->d;
   const int nbz = (h->C + 16) / 16, ntiles = nbz * (nbz + 1) / 2;
@@ -439,6 +464,11 @@ static void set_build_kernels(kb_handle* h) {
   h->mb = h->build_pipe ? ((ntiles + 1) / 2 <= 5 ? 5 : 7) : tb <= 1 ? 1 : tb <= 4 ? 4 : 7;
   unsigned mm = 0;
   for (int i = 0; i < h->N; ++i) mm |= 1u << d.model[i];
+  if (weighted(h) && h->build_pipe) {
+    h->fn_build = pick_build_pw<false>(h->mb, mm, h->buildp_wide);
+    h->fn_build_gn = pick_build_pw<true>(h->mb, mm, h->buildp_wide);
+    return;
+  }
   if (weighted(h)) {
     h->fn_build = h->fn_build_gn = pick_build_w(h->mb, mm);
     return;
@@ -447,16 +477,18 @@ static void set_build_kernels(kb_handle* h) {
   h->fn_build_gn = pick_build<true>(h->mb, mm, h->build_pipe, h->buildp_wide);
 }
 
-// A change of the robust settings: a weighted handle always builds with k_build (the layout KB_BUILD_PIPE=0 gives:
-// frames per block, block partial rows, threads, LDS), an unweighted one goes back to exactly what kb_create chose.
+// A change of the robust settings: a weighted handle builds with k_build (the layout KB_BUILD_PIPE=0 gives: frames
+// per block, block partial rows, threads, LDS) unless kb_set_robust_build chose the pipelined kernel, which keeps
+// kb_create's layout; an unweighted one goes back to exactly what kb_create chose.
 // Captured graphs hold the old kernels and arguments.
 // The setters ask robust_fits before they change anything, so a refused setting leaves the handle as it was.
-static bool robust_fits(const kb_handle* h, bool weighted_after) {
-  return kb_blay::build_fits(layout_rig(h), h->build_pipe0 && !weighted_after, h->F);
+static bool robust_fits(const kb_handle* h, bool weighted_after, int mode) {
+  return kb_blay::robust_fits(layout_rig(h), h->build_pipe0, mode == KB_ROBUST_BUILD_PIPE, weighted_after, h->F);
 }
+static bool robust_fits(const kb_handle* h, bool weighted_after) { return robust_fits(h, weighted_after, h->rb_build); }
 
 static int robust_relayout(kb_handle* h) {
-  h->build_pipe = h->build_pipe0 && !weighted(h);
+  h->build_pipe = kb_blay::robust_pipe(h->build_pipe0, h->rb_build == KB_ROBUST_BUILD_PIPE, weighted(h));
   h->build_threads = kb_blay::build_threads(layout_rig(h), h->build_pipe);
   set_build_kernels(h);
   return relayout(h);
@@ -1216,6 +1248,37 @@ int kb_set_corner_invR(kb_handle* h, const double* invR3, int32_t n) {
   return 0;
 }
 
+int kb_set_robust_build(kb_handle* h, int32_t mode) {
+  if (!h) return fail("kb_set_robust_build: null handle");
+  if (mode != KB_ROBUST_BUILD_GENERAL && mode != KB_ROBUST_BUILD_PIPE)
+    return fail("kb_set_robust_build: unknown mode (KB_ROBUST_BUILD_GENERAL or KB_ROBUST_BUILD_PIPE)");
+  if (mode == KB_ROBUST_BUILD_PIPE) {
+    if (sharded(h)) return fail("kb_set_robust_build: the pipelined weighted build runs on unsharded handles only");
+    if (!h->build_pipe0)
+      return fail("kb_set_robust_build: this rig builds with k_build (fewer than 4 or more than 8 cameras, or "
+                  "KB_BUILD_PIPE=0); the weighted k_buildp needs a rig that kb_create gave k_buildp");
+    unsigned mm = 0;
+    for (int i = 0; i < h->N; ++i) mm |= 1u << h->d.model[i];
+    if (!pick_build_pw<false>(5, mm, h->buildp_wide))
+      return fail("kb_set_robust_build: this measurement variant of the library has no weighted k_buildp");
+  }
+  if (mode == h->rb_build) return 0;
+  if (!weighted(h)) {  // nothing launched changes until the handle is weighted
+    h->rb_build = mode;
+    return 0;
+  }
+  if (!robust_fits(h, true, mode)) return fail("kb_set_robust_build: the k_build LDS budget is exceeded for this rig");
+  KB_HIP(hipSetDevice(h->device));
+  const int mode0 = h->rb_build;
+  h->rb_build = mode;
+  h->sys_valid = false;
+  if (robust_relayout(h)) {  // (drops the graphs and voids a prepared loop)
+    h->rb_build = mode0;
+    return robust_relayout_failed(h);
+  }
+  return 0;
+}
+
 int kb_get_mestimator_weights(kb_handle* h, double* w_out, double* s_out) {
   if (!h || !w_out) return fail("kb_get_mestimator_weights: null");
   if (!h->uploaded) return fail("kb_get_mestimator_weights: no observations");
@@ -1749,8 +1812,11 @@ struct GnFusedScope {
   ~GnFusedScope() { h->d = saved; }
 };
 
-// (a weighted handle runs its GN passes through the general pass: the fused kernels carry no weights)
-static bool gn_fused(const kb_handle* h, int policy) { return policy == 1 && h->gn_fuse && !weighted(h); }
+// (a weighted handle runs its GN passes through the general pass -- k_build carries no fused variant with weights --
+// unless it builds with the weighted k_buildp, KB_ROBUST_BUILD_PIPE)
+static bool gn_fused(const kb_handle* h, int policy) {
+  return policy == 1 && h->gn_fuse && (!weighted(h) || h->build_pipe);
+}
 
 // ev0 / ev1 (optional): HIP events recorded around the build kernel (kb_build_kernel_stats)
 static int enqueue_marg_pass(kb_handle* h);
@@ -2336,7 +2402,7 @@ static int capture_gn(kb_handle* h, int passes, bool with_end, hipGraphExec_t* o
 }
 
 int kb_gn_prepare(kb_handle* h, int32_t n_iter) {
-  if (h) KB_REFUSE_WEIGHTED(h, "kb_gn_prepare");
+  if (h) KB_REFUSE_WEIGHTED_GN(h, "kb_gn_prepare");
   if (!h || n_iter < 0) return fail("kb_gn_prepare: bad args");
   if (!h->uploaded) return fail("kb_gn_prepare: no observations");
   KB_HIP(hipSetDevice(h->device));
@@ -2378,7 +2444,7 @@ int kb_gn_prepare(kb_handle* h, int32_t n_iter) {
 }
 
 int kb_gn_launch(kb_handle* h, int32_t n_iter, double* seconds) {
-  if (h) KB_REFUSE_WEIGHTED(h, "kb_gn_launch");
+  if (h) KB_REFUSE_WEIGHTED_GN(h, "kb_gn_launch");
   if (!h || n_iter < 0) return fail("kb_gn_launch: bad args");
   if (h->gn_prepared != n_iter) return fail("kb_gn_launch: not prepared for this pass count (kb_gn_prepare)");
   h->gn_prepared = -1;
@@ -2426,7 +2492,7 @@ int kb_gn_launch(kb_handle* h, int32_t n_iter, double* seconds) {
 }
 
 int kb_run_gn_iterations(kb_handle* h, int32_t n_iter, double* seconds) {
-  if (h) KB_REFUSE_WEIGHTED(h, "kb_run_gn_iterations");
+  if (h) KB_REFUSE_WEIGHTED_GN(h, "kb_run_gn_iterations");
   if (kb_gn_prepare(h, n_iter) < 0) return -1;
   return kb_gn_launch(h, n_iter, seconds);
 }

@@ -1367,7 +1367,10 @@ __device__ __forceinline__ void schur_tiles_accumulate6(const double* P, const d
 // MW: the most waves a block may have.  12 (8 cameras + 4 frame waves) caps the kernel at 168 VGPRs, so that two
 // 6-wave blocks share a CU; rigs with N + frame waves <= 8 whose view role compiles two projection models
 // (configs[2]) take MW = 8 (256 VGPRs, no spills, one block per CU) -- kb_capi.hip `buildp_wide`.
-template <int TT, bool GNF, unsigned MM, int MW>
+// WT: robust terms as in k_build<.., WT = true> (kb_set_robust_build(h, KB_ROBUST_BUILD_PIPE)): a view lane scales the
+//     two rows of its corner by sqrt(w) L^T before the LDS tile; the per-corner factor (rb_n > 1) travels with cid / y
+//     at each of their three load sites.  With GNF the candidate cost of the fused pass, H[15][15], is sum w s.
+template <int TT, bool GNF, unsigned MM, int MW, bool WT = false>
 __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse) {
   KB_MFMA_AGPR();
   pass_stamp(d);
@@ -1500,10 +1503,18 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
   double* VB1 = fpl + 8 * d.gframes;
   int cidn;  // view waves: lane = corner of a 64-corner pass
   double2 yn;
+  RbFac Ln = {1.0, 0.0, 1.0};
+  bool rb_pc = false;  // per-corner factors (wave-uniform)
+  if constexpr (WT) {
+    rb_pc = d.rb_n > 1;
+    Ln = rb_uniform(d);
+  }
   {
     const int k = min(fv.x + lane, max(fv.y - 1, 0));
     cidn = d.cid[k];
     yn = d.y[k];
+    if constexpr (WT)
+      if (rb_pc) Ln = rb_load(d, k);
   }
 #pragma unroll
   for (int u = 0; u < 2; ++u)
@@ -1625,11 +1636,19 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
           if (stv && pass < 2) KB_TSB(d, sto + 4 * pass);
           const int cid = cidn;
           const double2 yv = yn;
+          const RbFac Lv = Ln;
+          (void)Lv;
           if (base + 64 < o1) {  // software-pipelined: next pass's corner ids and keypoints
             const int kn = min(k + 64, o1 - 1);
             cidn = d.cid[kn];
             yn = d.y[kn];
+            if constexpr (WT)
+              if (rb_pc) Ln = rb_load(d, kn);
           }
+#if defined(KB_CORNER_OLD) || defined(KB_SYRK16) || defined(KB_CORNER_CLAMP) || defined(KB_CORNER_NOZERO) || \
+    defined(KB_DIAG_NOPROJ) || defined(KB_DIAG_NOSYRK)
+          static_assert(!WT, "the diagnostic and timing variants of k_buildp carry no robust weights");
+#endif
 #ifdef KB_CORNER_OLD
           double xu[16], xv[16];
 #pragma unroll
@@ -1729,6 +1748,16 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
 #pragma unroll
               for (int q = 0; q < 9; ++q) xr[6 + q] = (q < nin) ? Ji[KB_MAX_INTR * r + q] : 0.0;
               xr[15] = r ? yv.y - w : yv.x - u;  // column 15 carries e: H[:,15] = rhs part, H[15][15] = chi^2
+            }
+            if constexpr (WT) {  // rows -> sqrt(w) L^T rows as in k_build (the sign of a row is free); column 15: w s
+              double sq, wt;
+              rb_term(d, Lv, xu[15], xv[15], sq, wt);
+              const double sw = sqrt(wt), a00 = sw * Lv.l00, a10 = sw * Lv.l10, a11 = sw * Lv.l11;
+#pragma unroll
+              for (int q = 0; q < 16; ++q) {
+                xu[q] = a00 * xu[q] + a10 * xv[q];
+                xv[q] = a11 * xv[q];
+              }
             }
           }
 #endif
@@ -1903,6 +1932,8 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
           const int k = min(fvn.x + lane, max(fvn.y - 1, 0));
           cidn = d.cid[k];
           yn = d.y[k];
+          if constexpr (WT)
+            if (rb_pc) Ln = rb_load(d, k);
         }
         if (wave == 0 && it < 8) KB_TSB(d, 3 + 2 * it);
         if (it == 3 && wave < 8) KB_TSB(d, 144 + wave);
@@ -5860,7 +5891,7 @@ __device__ __forceinline__ void backsub_block(const KbDev& d, int gate, int do_u
           if constexpr (WT)
             cost += rb_cost(d, Lv, e0, e1);
           else
-            cost += e0 * e0 + e1 * e1;
+            cost += fma(e0, e0, e1 * e1);  // (as cost_views_block; rb_cost follows it)
         }
       }
       cost = wave_sum_d(cost);
@@ -5958,7 +5989,7 @@ __device__ __forceinline__ void cost_views_block(const KbDev& d, int which) {
       if constexpr (WT)
         acc += rb_cost(d, d.rb_n > 1 ? rb_load(d, k) : rb_uniform(d), e0, e1);
       else
-        acc += e0 * e0 + e1 * e1;
+        acc += fma(e0, e0, e1 * e1);  // the order the compiler's contraction gave; rb_cost follows it
     }
     acc = wave_sum_d(acc);
   }

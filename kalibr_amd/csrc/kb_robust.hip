@@ -1,6 +1,7 @@
 // kb_robust.hip -- robust reprojection terms: M-estimator weights and the corner invR (kb_set_mestimator,
 // kb_set_corner_invR).  Included by kb_kernels.hip (inside namespace kb) ahead of the kernels whose weighted
-// instantiations use it: k_build<.., WT = true>, k_cost_w, k_backsub_w; k_rw_weights is the query kernel.
+// instantiations use it: k_build<.., WT = true>, k_buildp<.., WT = true> (kb_set_robust_build), k_cost_w, k_backsub_w;
+// k_rw_weights is the query kernel.
 //
 // Reference semantics restated (paths relative to the reference repository, aslam_optimizer/aslam_backend):
 //   a term has the raw squared error s = e^T invR e = |sqrtInvR^T e|^2 (ErrorTerm.hpp(impl):156-161) and the weight
@@ -47,9 +48,12 @@ __device__ __forceinline__ void rb_term(const KbDev& d, const RbFac& L, double e
   w = rb_weight(d.rb_kind, d.rb_param, s);
 }
 
-// the weighted chi^2 of one term, w(s) s
+// the weighted chi^2 of one term, w(s) s.  s is formed as the unweighted cost kernels form e0^2 + e1^2,
+// fma(e0, e0, e1 * e1) (cost_views_block, backsub_block): with the identity factor and no estimator t0 = e0, t1 = e1
+// and w = 1 exactly, so the weighted cost kernels then return the bits of the unweighted ones (left to the compiler,
+// the contraction of t0 * t0 + t1 * t1 rounded the other product and the sums differed in the last place)
 __device__ __forceinline__ double rb_cost(const KbDev& d, const RbFac& L, double e0, double e1) {
-  double s, w;
-  rb_term(d, L, e0, e1, s, w);
-  return w * s;
+  const double t0 = L.l00 * e0 + L.l10 * e1, t1 = L.l11 * e1;
+  const double s = fma(t0, t0, t1 * t1);
+  return rb_weight(d.rb_kind, d.rb_param, s) * s;
 }

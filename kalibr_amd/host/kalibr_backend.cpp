@@ -468,6 +468,7 @@ void GpuLinearSystemSolver::initMatrixStructure(const CalibrationProblem& p, boo
   _built = false;
   _rhs_valid = false;
   _nCorners = (size_t)p.n_corners();
+  if (_robustBuild != RobustBuild::General) check(kb_set_robust_build(h, (int32_t)_robustBuild), "kb_set_robust_build");
   if (p.mEstimator) setMEstimatorPolicy(p.mEstimator);
   if (!p.cornerInvR.empty()) setCornerInvR(p.cornerInvR);
 }
@@ -491,6 +492,15 @@ void GpuLinearSystemSolver::setCornerInvR(const std::vector<double>& invR3) {
         "kb_set_corner_invR");
   _built = false;
   _rhs_valid = false;
+}
+
+void GpuLinearSystemSolver::setRobustBuild(RobustBuild mode) {
+  if (_h) {
+    check(kb_set_robust_build(static_cast<kb_handle*>(_h), (int32_t)mode), "kb_set_robust_build");
+    _built = false;
+    _rhs_valid = false;
+  }
+  _robustBuild = mode;
 }
 
 std::vector<double> GpuLinearSystemSolver::mEstimatorWeights(std::vector<double>* squaredErrors) {

@@ -362,6 +362,9 @@ struct GpuOptions {
   bool pcgAbsoluteTolerance = true;
 };
 
+/// The build kernel of a weighted GpuLinearSystemSolver (enum kb_robust_build, kb_set_robust_build)
+enum class RobustBuild { General = 0, Pipe = 1 };
+
 /// LinearSystemSolver whose build / solve / update / cost run on one MI355X (kalibr_hip.h).  The
 /// per-call methods mirror the reference solver one call at a time; optimizeOnDevice() runs the whole
 /// Optimizer2 loop device-resident (one captured graph per pass).
@@ -403,6 +406,12 @@ class GpuLinearSystemSolver : public ProblemLinearSystemSolver {
   bool supportsRobustTerms() const override { return true; }
   void setMEstimatorPolicy(std::shared_ptr<const MEstimator> m) override;
   void setCornerInvR(const std::vector<double>& invR3) override;
+  /// kb_set_robust_build: General (default) builds a weighted problem with k_build and runs GN through the general
+  /// pass; Pipe keeps the pipelined build of rigs with 4..8 cameras, so that Optimizer2::optimizeOnDevice() with the GN
+  /// policy runs fused.  Throws Exception with the C-ABI's message when the rig (or a sharded handle) has no pipelined
+  /// weighted build; the mode is then unchanged.  Before initMatrixStructure the mode is kept and applied there.
+  void setRobustBuild(RobustBuild mode);
+  RobustBuild robustBuild() const { return _robustBuild; }
   std::vector<double> mEstimatorWeights(std::vector<double>* squaredErrors = nullptr) override;
   std::vector<std::array<double, 6>> reprojectionErrorStatistics() override;  // kb_reprojection_error_stats
   void setState(const std::vector<double>& s);
@@ -424,6 +433,7 @@ class GpuLinearSystemSolver : public ProblemLinearSystemSolver {
   GpuOptions _opt;
   size_t _C = 0, _F = 0, _N = 0;
   size_t _nCorners = 0;
+  RobustBuild _robustBuild = RobustBuild::General;
   std::vector<int32_t> _models;
   double _conditioner = 0.0;
   bool _built = false;
