@@ -554,24 +554,57 @@ __device__ __forceinline__ void schur_tiles_store(double* prow_schur, int C, con
 }
 
 // expanded partials (GN fused, C > 64): the tiles' entries stored as EX - sum, EX = the block's camera-block expansion
-// (same packing: S upper | b), so that the column sums are S - lambda^2 I and b themselves
+// (same packing: S upper | b), so that the column sums are S - lambda^2 I and b themselves.  Transposed tiles only
+// (schur_tiles_accumulate6: lane l, reg r -> tile row l & 15, column (l >> 4) + 4 r).
+// This runs once per block, after the last frame: its instructions are fetched cold and nothing overlaps it, so it is
+// written for few instructions and one LDS round per group of tiles:
+//   - per tile and lane one packed index ub (column c0 = 16 jj + (l >> 4) of row rg), a step s and a count d; the
+//     lane's four entries are columns c0 + 4 r, at ub + r s - q r (r - 1) (upper_index(c + 4, rg) - upper_index(c, rg)
+//     = 4 (C - c) - 10: s = 4 (C - c0) - 10, q = 8; row C, the b row, is contiguous: s = 4, q = 0), valid iff 4 r <= d
+//     with d = min(rg, C - 1) - c0 (-1: row past C, or a wave with fewer than TW tiles);
+//   - the EX reads of a group issued unconditionally at a clamped index and kept together, then the differences
+//     stored under the count test.  Groups of two tiles (8 reads in flight): all 28 values and offsets beside acc[7]
+//     do not fit the kernel's 168 registers, groups of four tiles fit but spill in the KB_STAMPS build, and groups of
+//     two measure the same as groups of four (profiles/r13/ab_variants_c4.json).
 template <int TW, bool kT = false>
 __device__ __forceinline__ void schur_tiles_store_x(double* prow_schur, int C, const int* tii, const int* tjj,
                                                     const v4d* acc, const double* EX) {
-  const int lane = threadIdx.x & 63, Wt = C * (C + 1) / 2;
+  static_assert(kT, "transposed tiles only");
+  const int lane = threadIdx.x & 63, ra = lane & 15, k0 = lane >> 4, Wt = C * (C + 1) / 2;
+  constexpr int GT = TW > 2 ? 2 : TW;
 #pragma unroll
-  for (int t = 0; t < TW; ++t) {
-    if (tii[t] < 0) break;
+  for (int t0 = 0; t0 < TW; t0 += GT) {
+    int u[GT][4], dd[GT];
+    double ex[GT][4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int ra = kT ? (lane & 15) : (lane >> 4) + 4 * r, ca = kT ? (lane >> 4) + 4 * r : (lane & 15);
-      const int rg = 16 * tii[t] + ra, cg = 16 * tjj[t] + ca;
-      if (rg < C && cg <= rg) {
-        const int u = upper_index(cg, rg, C);
-        prow_schur[u] = EX[u] - acc[t][r];
-      } else if (rg == C && cg < C) {
-        prow_schur[Wt + cg] = EX[Wt + cg] - acc[t][r];
+    for (int g = 0; g < GT; ++g) {
+      const int t = t0 + g;
+      if (t >= TW) break;  // unrolled: no code for the rest of a short last group
+      const int rg = 16 * tii[t] + ra, c0 = 16 * tjj[t] + k0;
+      const bool brow = rg == C;
+      const int ub = brow ? Wt + c0 : upper_index(c0, rg, C);
+      const int s = brow ? 4 : 4 * (C - c0) - 10, q = brow ? 0 : 8;
+      dd[g] = (tii[t] >= 0 && rg <= C) ? min(rg, C - 1) - c0 : -1;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        u[g][r] = ub + r * s - q * r * (r - 1);
+        ex[g][r] = EX[4 * r <= dd[g] ? u[g][r] : 0];
       }
+    }
+#pragma unroll
+    for (int g = 0; g < GT; ++g) {
+      if (t0 + g >= TW) break;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) KB_KEEP(ex[g][r]);
+    }
+#pragma unroll
+    for (int g = 0; g < GT; ++g) {
+      const int t = t0 + g;
+      if (t >= TW) break;
+      const v4d av = acc[t];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (__builtin_expect(4 * r <= dd[g], 1)) prow_schur[u[g][r]] = ex[g][r] - av[r];
     }
   }
 }
@@ -1961,6 +1994,7 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
             Xw[c2 * XS + rb] = o2;
           }
           KB_WAVE_SYNC();
+          if (stv && wave) KB_TSB(d, 76);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             hv[q] = Xw[(mrow + 4 * q) * XS + mcol];
@@ -1987,12 +2021,24 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
         v4d dv = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int st = 0; st < 2; ++st) dv = __builtin_amdgcn_mfma_f64_16x16x4f64(hv[st], gb[st], dv, 0, 0, 0);
+#ifdef KB_STAMPS
+        if (stv && wave) {  // the pair's result in hand, not only issued
+          KB_KEEP(dv[0]);
+          KB_TSB(d, 77);
+        }
+#endif
         double pa[2];  // A = P_v[:, d]: lane supplies P_v[i16][k0 + 4 st] = D[k0 + 4 st][i16]
 #pragma unroll
         for (int st = 0; st < 2; ++st) pa[st] = (k0 + 4 * st < 6) ? dv[st] : 0.0;
         v4d t2 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int st = 0; st < 2; ++st) t2 = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[st], gb[st], t2, 0, 0, 0);
+#ifdef KB_STAMPS
+        if (stv && wave) {
+          KB_KEEP(t2[0]);
+          KB_TSB(d, 78);
+        }
+#endif
         // this camera's share P_v K_{v,j} of the baseline columns is formed by the frame waves (their per-frame chain
         // has the slack): the A operand goes to LDS in its register layout, buffer it & 1
         if (cam > 0) {
@@ -2089,8 +2135,12 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
       // the view waves meet (an LDS counter: the frame waves are not at a block barrier now) before the baseline
       // tiles read every camera's T_i
       KB_WAVE_SYNC();
+      const bool stx = wave == 0 || wave == N - 1;  // diagnostic stamps: the first and the last camera's wave
+      const int sxo = wave == 0 ? 64 : 68;
+      if (stx) KB_TSB(d, sxo);
       if (lane == 0) atomicAdd(&xcnt, 1);
       while (__hip_atomic_load(&xcnt, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < N) __builtin_amdgcn_s_sleep(1);
+      if (stx) KB_TSB(d, sxo + 1);
       const int ntb = (NB + 15) >> 4;
       for (int tq = wave; tq < ntb * (ntb + 1) / 2; tq += N) {  // tile (ta, tb), ta <= tb, upper tiles in row order
         int ta = 0, q = tq;
@@ -2118,18 +2168,26 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
           if (row <= col && col < NB) EX[upper_index(CI + row, CI + col, C)] = acc[r];
         }
       }
-      for (int n = tid; n < NB; n += 64 * N) {
-        double g = 0.0;
-        for (int i = n / 6 + 1; i < N; ++i) g += gB[i * 48 + n];
-        EX[Wt + CI + n] = g;
+      if (wave == 0) KB_TSB(d, 79);
+      // g_B and the cost on the last view wave: the baseline tiles number fewer than N ((ntb, N) = (1, 2), (1, 3),
+      // (2, 4), (2, 5), (2, 6), (3, 7), (3, 8): 1, 1, 3, 3, 3, 6, 6), so that wave has no tile, and wave 0 (which
+      // the frame waves wait for at the next barrier) has its tile only
+      if (wave == N - 1) {
+        for (int n = lane; n < NB; n += 64) {
+          double g = 0.0;
+          for (int i = n / 6 + 1; i < N; ++i) g += gB[i * 48 + n];
+          EX[Wt + CI + n] = g;
+        }
+        if (lane == 0) {
+          double sc = 0.0;
+          for (int i = 0; i < N; ++i) sc += cc[i];
+          prow[C] = sc;  // the block's chi^2 (the cost column)
+        }
       }
-      if (tid == 0) {
-        double sc = 0.0;
-        for (int i = 0; i < N; ++i) sc += cc[i];
-        prow[C] = sc;  // the block's chi^2 (the cost column)
-      }
+      if (stx) KB_TSB(d, sxo + 2);
     }
     __syncthreads();  // the frame waves' last barrier (after the last frame's sums and elimination)
+    if (wave == 0 || wave == N - 1) KB_TSB(d, wave == 0 ? 67 : 71);
     if (!xp) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {  // the camera's local sums, upper packed
@@ -2268,15 +2326,27 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
       }
       if (it < G) __syncthreads();  // the view waves' frame it is in VB[it & 1]
     }
+    if (fw == 0) KB_TSB(d, 72);
     __syncthreads();  // the view waves' last barrier (their expansion of the block's camera sums is done)
+    if (fw == 0) KB_TSB(d, 73);
     if (fuse && !xp) schur_tiles_store<TT, true>(prow + N * 136, C, tii, tjj, acc);
     // expanded partials: the view waves expanded the camera block during the last frame's elimination
     if (xp) schur_tiles_store_x<TT, true>(prow + N * 136, C, tii, tjj, acc, sm);
+    if (fw == 0) KB_TSB(d, 74);
+#ifdef KB_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row's stores acknowledged, not only issued
+    if (fw == 0) KB_TSB(d, 75);
+#endif
   }
   if (xp && vw) {
     // expanded partials: the g_c columns of the block's partial row (the cost column was written in the idle phase)
     const double* EX = sm;
-    for (int e = tid; e < C; e += 64 * N) prow[e] = EX[W - C + e];
+    for (int e0 = 0; e0 < C; e0 += 64 * N) {  // the read outside the bounds test, at a clamped index
+      const int e = e0 + tid;
+      const double v = EX[W - C + min(e, C - 1)];
+      KB_KEEP(v);
+      if (e < C) prow[e] = v;
+    }
   }
   __syncthreads();  // okl final
   if (wave == 0) KB_TSB(d, 63);

@@ -40,6 +40,19 @@ names[180] = "    [fw0] f2 products met"
 for w in range(8):
     names[144 + w] = f"      [view wave {w}] f3 SYRK done"
     names[152 + w] = f"      [view wave {w}] f3 expansion done"
+for w, o in (("view wave 0", 64), ("last view wave", 68)):  # the expanded-partials epilogue (C > 64, GN fused)
+    names[o] = f"  [{w}] epilogue step 1 done"
+    names[o + 1] = f"  [{w}] epilogue view waves met"
+    names[o + 2] = f"  [{w}] epilogue step 2 done (at the last barrier)"
+    names[o + 3] = f"  [{w}] epilogue last barrier left"
+names[72] = "  [fw0] at the last view barrier"
+names[73] = "  [fw0] last view barrier left"
+names[74] = "  [fw0] partial-row stores issued"
+names[75] = "  [fw0] partial-row stores acknowledged"
+names[76] = "  [last view wave] f2 expansion: rebuild read back"
+names[77] = "  [last view wave] f2 expansion: MFMA pair 1 done"
+names[78] = "  [last view wave] f2 expansion: MFMA pair 2 done"
+names[79] = "  [view wave 0] epilogue step 2 baseline tile done"
 names[140] = "    [fw0] f2 elimination entry"
 names[141] = "    [fw0] f2 6x6 LDL^T done"
 names[142] = "    [fw0] f2 column slot 0 solved+stored"
