@@ -29,8 +29,14 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 
 #define KB_WAVE_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 // an (empty) use of an accumulation register: the compiler then selects the AGPR-accumulator form of every MFMA in
-// the kernel.  With VGPR accumulators, a wave issuing back-to-back f64 MFMAs slows the VALU instructions of the other
-// waves on its SIMD ~5x (38 vs 7 cycles each); with AGPR accumulators ~2x (tools/micro/simd_share.hip)
+// the kernel.  With VGPR accumulators, a wave issuing back-to-back v_mfma_f64_16x16x4 slows the VALU instructions of
+// the other waves on its SIMD ~5x (38 vs 7 cycles each); with AGPR accumulators ~2x (12-14 cycles, the MFMA wave
+// itself at 93 instead of 64 cycles per MFMA).  That holds for streams of 16x16x4 (k_solve<0>, the covariance
+// kernels).  k_buildp's SYRK stream (five v_mfma_f64_4x4x4 per step between LDS reads) slows them the same in
+// either form (13.7 / 14.2 cycles per dependent f64 FMA, 19.4 / 19.4 for independent chains; 21 cycles per MFMA
+// both), while a kernel that uses AGPRs has its register budget split and parks values in AGPRs behind
+// v_accvgpr_* copies: k_buildp chooses per instantiation family (buildp_vgpr_acc).  tools/micro/simd_share.hip,
+// profiles/r14/simd_share.txt
 #define KB_MFMA_AGPR() asm volatile("" ::"a"(0))
 // materialise a loaded value at this point (an empty asm use): loads issued above cannot sink below it
 #define KB_KEEP(x) asm volatile("" ::"v"(x))
@@ -1397,6 +1403,40 @@ __device__ __forceinline__ void schur_tiles_accumulate6(const double* P, const d
   }
 }
 
+// The register arrangement of k_buildp, per instantiation family.
+// KB_BUILDP_VGPR: the families whose MFMAs take VGPR accumulators (no AGPR use in the kernel, so the whole register
+//   budget is architectural and nothing is parked in AGPRs behind v_accvgpr_* copies): bit 0 the 12-wave one-model
+//   unweighted instantiations, bit 1 the 8-wave unweighted ones, bit 2 every other one (weighted; 12-wave multi-model).
+// KB_BUILDP_HOIST: what a view wave forms once per block instead of once per frame: bit 0 its lane id is opaque once
+//   per block in the 12-wave one-model unweighted instantiations (the compiler then keeps the lane-dependent
+//   addresses, masks and predicates of the SYRK and the expansion tail in registers; the weighted and the 12-wave
+//   multi-model view roles have no registers for them), bit 3 the same in the 8-wave two-model unweighted ones (the
+//   all-model one would go to scratch); bit 2, in the same families, the camera's first intrinsic column (ctab) is
+//   read from LDS once.  Bit 1: the frame waves' lane id once per block (measured, not kept).
+// The product: 3 and 13 (measured per family, profiles/r14/; 0 and 0 are the arrangement before round 14, which the
+// unmeasured families keep).
+#ifndef KB_BUILDP_VGPR
+#define KB_BUILDP_VGPR 3
+#endif
+#ifndef KB_BUILDP_HOIST
+#define KB_BUILDP_HOIST 13
+#endif
+template <unsigned MM, int MW, bool WT>
+constexpr bool buildp_vgpr_acc() {
+  return ((KB_BUILDP_VGPR) >> (WT ? 2 : MW == 8 ? 1 : mm_nintr<MM>() != 0 ? 0 : 2)) & 1;
+}
+template <unsigned MM, int MW, bool WT>
+constexpr bool buildp_view_lane_once() {
+  if (WT) return false;
+  return MW == 8 ? (((KB_BUILDP_HOIST) >> 3) & 1) && __builtin_popcount(MM) <= 2
+                 : ((KB_BUILDP_HOIST) & 1) && mm_nintr<MM>() != 0;
+}
+template <unsigned MM, int MW, bool WT>
+constexpr bool buildp_view_cic_once() {
+  if (WT || !((KB_BUILDP_HOIST) & 4)) return false;
+  return MW == 8 ? __builtin_popcount(MM) <= 2 : mm_nintr<MM>() != 0;
+}
+
 // MW: the most waves a block may have.  12 (8 cameras + 4 frame waves) caps the kernel at 168 VGPRs, so that two
 // 6-wave blocks share a CU; rigs with N + frame waves <= 8 whose view role compiles two projection models
 // (configs[2]) take MW = 8 (256 VGPRs, no spills, one block per CU) -- kb_capi.hip `buildp_wide`.
@@ -1405,7 +1445,7 @@ __device__ __forceinline__ void schur_tiles_accumulate6(const double* P, const d
 //     at each of their three load sites.  With GNF the candidate cost of the fused pass, H[15][15], is sum w s.
 template <int TT, bool GNF, unsigned MM, int MW, bool WT = false>
 __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse) {
-  KB_MFMA_AGPR();
+  if constexpr (!buildp_vgpr_acc<MM, MW, WT>()) KB_MFMA_AGPR();
   pass_stamp(d);
   KbCtrl* c = d.ctrl;
   extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -1626,12 +1666,18 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
     const double* Lc = cst[cam];
     const double* intr = cst[cam] + 12;
     v4d creg = {0.0, 0.0, 0.0, 0.0};  // the camera's local sums over the block's frames
+    int lane_v = threadIdx.x & 63;
+    if constexpr (buildp_view_lane_once<MM, MW, WT>()) asm volatile("" : "+v"(lane_v));
+    int cic = 0;  // the camera's first intrinsic column, read once where the family has it so (else per store)
+    if constexpr (buildp_view_cic_once<MM, MW, WT>()) cic = __builtin_amdgcn_readfirstlane(ctab[0][cam]);
     for (int it = 0; it < G; ++it) {
       {
         // ---------------- phase B: view (f, cam)
         const int f = f0 + it;
-        int lane = threadIdx.x & 63;  // opaque per frame (see the frame waves)
-        asm volatile("" : "+v"(lane));
+        // opaque per frame (see the frame waves), or once per block (buildp_view_lane_once): what depends on the
+        // lane alone is then formed ahead of the frames
+        int lane = lane_v;
+        if constexpr (!buildp_view_lane_once<MM, MW, WT>()) asm volatile("" : "+v"(lane));
         const int mrow = lane >> 4, mcol = lane & 15;
         if (wave == 0 && it < 8) KB_TSB(d, 2 + 2 * it);
         double* vb = (it & 1) ? VB1 : VB;
@@ -2051,8 +2097,9 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
           const int i = k0 + 4 * r;
           if (i16 < 6) {
             if (i >= 6 && i < 6 + nin) {
-              Pi[i16 * CZ + ctab[0][cam] + i - 6] = dv[r];
-              if (!gfu) d.Hfc[((size_t)f * 6 + i16) * C + ctab[0][cam] + i - 6] = dv[r];
+              const int ci = buildp_view_cic_once<MM, MW, WT>() ? cic : ctab[0][cam];
+              Pi[i16 * CZ + ci + i - 6] = dv[r];
+              if (!gfu) d.Hfc[((size_t)f * 6 + i16) * C + ci + i - 6] = dv[r];
             } else if (i == 15) {
               dgv[i16] = dv[r];
             }
@@ -2215,6 +2262,10 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
     // spread over waves 0..1), then H_ff (its upper triangle, mirrored: 21 sums) and g_f on the cheapest wave: one
     // lane per output (243 at N = 7) over the 4 frame waves; the intrinsic columns are in place
     const int nbl = 36 * (N - 1), nsum = nbl + 27;
+#if (KB_BUILDP_HOIST) & 2
+    int lane_f = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane_f));
+#endif
     for (int it = 0; it <= G; ++it) {
       if (it > 0) {
         // ---------------- phase A: sums of frame f = f0 + it - 1 over its views (camera order), the frame waves' share
@@ -2302,8 +2353,12 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
         const int f = f0 + it - 1;
         // an opaque lane id per frame: the lane-dependent addresses and selects of the elimination are recomputed
         // here instead of being hoisted out of the loop (which spills at this kernel's register budget)
+#if (KB_BUILDP_HOIST) & 2
+        const int lane = lane_f;
+#else
         int lane = threadIdx.x & 63;
         asm volatile("" : "+v"(lane));
+#endif
         if (fw == 0 && it <= 8) KB_TSB(d, 20 + 4 * (it - 1));
         double* P = (((it - 1) & 1) ? VB1 : VB) + N * 44;
 #ifdef KB_DIAG_NOFW
