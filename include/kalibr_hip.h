@@ -419,6 +419,9 @@ int kb_selftest_mfma(double* max_err);
  *                 gyro  w_m = w_b(t) + b_g,  w_b = -C^T S(theta) theta_dot (BSplinePose.cpp:207-219)
  *                 accel a_m = C^T (p_ddot(t) - g_w) + b_a                  (cf. BSplinePose.cpp:175-180)
  *                 whitened by 1/sigma_gyro, 1/sigma_acc.
+ *   robust terms  M-estimators on the reprojection, gyro and accelerometer terms and a corner invR
+ *                 (kb_sp_set_mestimator / kb_sp_set_corner_invR, at the end of this block); without them every
+ *                 corner has invR = I and every term the weight 1.
  * State:   intr [N][KB_MAX_INTR] | base [N-1][7] | T_c0_b [7] | b_g [3] | b_a [3] | g_w [3] | coeff [K][6]
  * Columns: [intr | B_j (dphi, dt) | T_c0_b (dphi, dt) | b_g | b_a | g_w | coeff 0..K-1 (6 each)]
  * Knot vector: non-decreasing, n_knots = K + order; the device path supports order 4 (cubic).
@@ -489,6 +492,32 @@ int kb_sp_kernel_stats(kb_sp_handle* h, int32_t n, double* ms_out6, double* fram
 /* Device time (ms, HIP events around each launch on the handle's stream, averaged over n launches inside built
  * passes) and algorithmic bytes per launch of the node-assembly kernel (the pass's largest single launch). */
 int kb_sp_assemble_stats(kb_sp_handle* h, int32_t n, double* ms, double* bytes);
+
+/* Robust terms on the spline path: the semantics of kb_set_mestimator / kb_set_corner_invR above, per
+ * term family.  A term has the raw squared error s and the weight w = getWeight(s) of its family's estimator:
+ *   KB_SP_TERM_REPROJECTION  one term per corner,         s = e^T invR e
+ *   KB_SP_TERM_GYRO          one 3-row term per IMU sample, s = |e_g|^2 of the whitened residual
+ *   KB_SP_TERM_ACCEL         one 3-row term per IMU sample, s = |e_a|^2
+ * The cost is sum w s over the three families (always weighted) plus the motion and prior costs, which take no
+ * estimator (the priors keep their own invR); the rows of a term are sqrt(w) sqrtInvR^T [J | e], invR on corners only;
+ * w is evaluated at the state that is linearised.  For KB_MEST_BLAKE_ZISSERMAN param is epsilon itself: the reference's
+ * computeEpsilon needs the chi^2 quantile of the term's dimension, which has no closed form for the IMU families
+ * (df = 3), so it is the caller's to compute.
+ * A handle with any estimator != NONE or an invR set is "weighted": kb_sp_eval_cost, kb_sp_build, kb_sp_get_system,
+ * kb_sp_get_rhs, kb_sp_solve, kb_sp_optimize (LM and GN), kb_sp_run_gn_iterations, kb_sp_kernel_stats and
+ * kb_sp_assemble_stats work on it through the same calls.  There is no build without the estimator (the spline path
+ * has no covariance consumer).  Every setter voids the built system and the captured GN pass; a refused call leaves the
+ * handle as it was; a handle whose settings are all cleared launches exactly the kernels of a fresh one.
+ * kb_sp_set_mestimator: before or after kb_sp_upload; m == NULL or kind NONE clears the family's estimator.
+ * kb_sp_set_corner_invR: as kb_set_corner_invR (n == 0 or NULL clears, 1 one matrix for every corner, n_corners one per
+ * corner in upload order, each positive definite); n == n_corners needs kb_sp_upload first.  kb_sp_upload is refused on
+ * a handle that has observations, so a per-corner invR never outlives the corners it was given for.
+ * kb_sp_get_mestimator_weights: w and s of every term of one family at the current state, upload order: [n_corners]
+ * or [n_imu]; s_out may be NULL. */
+enum kb_sp_term { KB_SP_TERM_REPROJECTION = 0, KB_SP_TERM_GYRO = 1, KB_SP_TERM_ACCEL = 2 };
+int kb_sp_set_mestimator(kb_sp_handle* h, int32_t term, const kb_mestimator* m);
+int kb_sp_set_corner_invR(kb_sp_handle* h, const double* invR3, int32_t n);
+int kb_sp_get_mestimator_weights(kb_sp_handle* h, int32_t term, double* w_out, double* s_out);
 
 #ifdef __cplusplus
 }

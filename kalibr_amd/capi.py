@@ -38,11 +38,13 @@ EXPORTS = [
     "kb_sp_solve", "kb_sp_get_rhs", "kb_sp_apply_update", "kb_sp_revert", "kb_sp_get_system", "kb_sp_optimize",
     "kb_sp_get_trace", "kb_sp_run_gn_iterations", "kb_sp_kernel_stats", "kb_sp_assemble_stats", "kb_sp_set_motion_error",
     "kb_sp_set_position_priors",
+    # robust terms on the spline path (kb_sp_set_corner_invR is in EXPORTS_MIXED_CASE below)
+    "kb_sp_set_mestimator", "kb_sp_get_mestimator_weights",
 ]
 # declared symbols with an upper-case letter (the reference's setInvR spelling).  EXPORTS holds the lower-case names
 # that tests/test_capi_boundary.py's header pattern matches; tests/test_robust_ref.py checks the two lists together
 # against every kb_* name of the header, whatever its case
-EXPORTS_MIXED_CASE = ["kb_set_corner_invR"]
+EXPORTS_MIXED_CASE = ["kb_set_corner_invR", "kb_sp_set_corner_invR"]
 
 
 class KbError(RuntimeError):
@@ -103,6 +105,7 @@ POLICIES = {"lm": 0, "gn": 1, "dogleg": 2}
 # kb_mestimator_kind; the parameter is k | sigma^2 | sigma^2 | epsilon
 MESTIMATORS = {"none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3, "blake_zisserman": 4}
 ROBUST_BUILDS = {"general": 0, "pipe": 1}  # enum kb_robust_build
+SP_TERMS = {"reprojection": 0, "gyro": 1, "accel": 2}  # enum kb_sp_term
 
 
 def blake_zisserman_epsilon(df, p_cut, w_cut):
@@ -211,6 +214,9 @@ def lib():
         L.kb_sp_assemble_stats.argtypes = [C.c_void_p, C.c_int32, dp, dp]
         L.kb_sp_set_motion_error.argtypes = [C.c_void_p, dp, C.c_int32]
         L.kb_sp_set_position_priors.argtypes = [C.c_void_p, C.c_int32, dp, dp, dp]
+        L.kb_sp_set_mestimator.argtypes = [C.c_void_p, C.c_int32, C.POINTER(MEstimator)]
+        L.kb_sp_set_corner_invR.argtypes = [C.c_void_p, dp, C.c_int32]
+        L.kb_sp_get_mestimator_weights.argtypes = [C.c_void_p, C.c_int32, dp, dp]
         _lib = L
     return _lib
 
@@ -625,6 +631,33 @@ class SplineSolver:
                      np.ascontiguousarray(N, dtype=np.float64).reshape(-1, 3, 3))
         t, pr, n3 = self._pos
         _check(lib().kb_sp_set_position_priors(self.h, t.size, _d(t), _d(pr), _d(n3)))
+
+    def set_mestimator(self, term, kind="none", param=0.0):
+        """ErrorTerm::setMEstimatorPolicy for every term of one family: term in SP_TERMS, kind in MESTIMATORS, param =
+        k | sigma^2 | sigma^2 | epsilon; "none" / None clears it."""
+        t = SP_TERMS[term] if isinstance(term, str) else int(term)
+        k = MESTIMATORS[kind or "none"]
+        if k == 0:
+            _check(lib().kb_sp_set_mestimator(self.h, t, None))
+        else:
+            m = MEstimator(k, float(param))
+            _check(lib().kb_sp_set_mestimator(self.h, t, C.byref(m)))
+
+    def set_corner_invR(self, invR3=None):
+        """ErrorTermFs::setInvR: None clears; [a, b, c] one symmetric 2x2 for every corner; [n_corners][3] one each."""
+        if invR3 is None:
+            _check(lib().kb_sp_set_corner_invR(self.h, None, 0))
+            return
+        a = np.ascontiguousarray(invR3, dtype=np.float64).reshape(-1, 3)
+        _check(lib().kb_sp_set_corner_invR(self.h, _d(a), a.shape[0]))
+
+    def mestimator_weights(self, term):
+        """(w, s) of every term of one family at the current state, upload order."""
+        t = SP_TERMS[term] if isinstance(term, str) else int(term)
+        n = self.prob.n_corners if t == 0 else self.prob.n_imu
+        w, s = np.zeros(n), np.zeros(n)
+        _check(lib().kb_sp_get_mestimator_weights(self.h, t, _d(w), _d(s)))
+        return w, s
 
     def set_state(self, state):
         st = np.ascontiguousarray(state, dtype=np.float64)

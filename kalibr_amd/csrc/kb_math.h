@@ -342,4 +342,23 @@ __device__ __forceinline__ void project_jac(int model, const double* in, double 
   }
 }
 
+// getWeight(s) of M-estimator `kind` (KB_MEST_*) with parameter p (aslam_backend/src/MEstimatorPolicies.cpp): the
+// rig's robust terms (kb_robust.hip) and the spline path's (kb_spline.hip).  kind is wave-uniform at every caller, so
+// the square root, the divisions and the exponential are issued only for the estimator that is set.
+__device__ __forceinline__ double rb_weight(int kind, double p, double s) {
+  switch (kind) {
+    case KB_MEST_HUBER: return s < p * p ? 1.0 : p / sqrt(s);  // MEstimatorPolicies.cpp:64-66
+    case KB_MEST_CAUCHY: return 1.0 / (1.0 + s / p);           // :46-49
+    case KB_MEST_GEMAN_MCCLURE: {                               // :31-34
+      const double se = p + s;
+      return p / (se * se);
+    }
+    case KB_MEST_BLAKE_ZISSERMAN: {                             // :104-106
+      const double ex = exp(-s);
+      return ex / (ex + p);
+    }
+    default: return 1.0;  // NoMEstimator (:17-19)
+  }
+}
+
 }  // namespace kb

@@ -12,22 +12,7 @@
 // The estimator kind and the invR mode are kernel arguments (wave-uniform branches); the per-corner factors are the
 // only added loads (24 B per corner, rb_n > 1).
 
-// getWeight(s) of estimator `kind` (KB_MEST_*) with parameter p
-__device__ __forceinline__ double rb_weight(int kind, double p, double s) {
-  switch (kind) {
-    case KB_MEST_HUBER: return s < p * p ? 1.0 : p / sqrt(s);  // MEstimatorPolicies.cpp:64-66
-    case KB_MEST_CAUCHY: return 1.0 / (1.0 + s / p);           // :46-49
-    case KB_MEST_GEMAN_MCCLURE: {                               // :31-34
-      const double se = p + s;
-      return p / (se * se);
-    }
-    case KB_MEST_BLAKE_ZISSERMAN: {                             // :104-106
-      const double ex = exp(-s);
-      return ex / (ex + p);
-    }
-    default: return 1.0;  // NoMEstimator (:17-19)
-  }
-}
+// getWeight(s) of estimator `kind` with parameter p: rb_weight (kb_math.h, shared with the spline path)
 
 // Cholesky factor (l00, l10, l11) of a corner's invR
 struct RbFac {

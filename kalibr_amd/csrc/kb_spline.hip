@@ -2,6 +2,9 @@
 // camera ReprojectionError terms through the spline pose and IMU gyro / accelerometer terms, assembled
 // into the block-banded normal equations and solved by block cyclic reduction + a Schur complement onto
 // the camera / IMU block.  Entry points: include/kalibr_hip.h (kb_sp_*).
+// Robust terms: M-estimators on the reprojection, gyro and accelerometer terms and a corner invR, in the
+// WT = true instantiations of k_sp_frames, imu_cc_wave, k_sp_assemble and k_sp_cost_frames; an unweighted handle
+// launches the WT = false ones, the kernels it always launched.
 //
 // Reference map (paths relative to the reference repository):
 //   BSplinePose::transformationAndJacobian      bsplines/src/BSplinePose.cpp:26-41 (J = JT JS)
@@ -143,7 +146,38 @@ struct SpDev {
   double* xs;             // [n][18] the nodes' spline steps x_j = X_j v (zs)
   double* bm;             // [n][18][37] L_j^-T [Z_Uin,j | Z_U,j | Z_R,j v] (zs, k_sp_bprep)
   double* irec;           // [IRQ][M] per-sample IMU records (k_sp_imu_cc -> k_sp_assemble): T1 | T2 | T3 | C^T | e
+  // robust terms (kb_sp_set_mestimator / kb_sp_set_corner_invR), read by the WT instantiations only
+  int rw_kind[3];         // KB_MEST_* of the reprojection | gyro | accel terms (compile-time indices only: sp_cam_arg)
+  double rw_par[3];
+  int rb_n;               // corner invR: 0 the identity | 1 rb_l for every corner | n_corners: rb_L
+  double rb_l[3];         // lower Cholesky factor (l00, l10, l11) of the invR every corner shares
+  const double* rb_L;     // [n_corners][3] per-corner factors
+  double* irw;            // [2][M] per-sample ig sqrt(w_g) | ia sqrt(w_a) (imu_cc_wave<true> -> k_sp_assemble<true>)
+  int q_term;             // k_sp_weights only: the family (kb_sp_term) and its outputs
+  double *q_w, *q_s;
 };
+
+using kb::rb_weight;
+
+// sqrt(w) of a term whose estimator is `kind` (wave-uniform): no square root without an estimator
+__device__ __forceinline__ double sp_sqrt_w(int kind, double w) { return kind == KB_MEST_NONE ? 1.0 : sqrt(w); }
+
+// Cholesky factor of a corner's invR (kb_robust.hip's convention: L^T e = (l00 e0 + l10 e1, l11 e1)): the uniform one,
+// or corner k's (one 24-byte load that depends on nothing but k, so it travels with cid / y)
+struct SpFac {
+  double l00, l10, l11;
+};
+__device__ __forceinline__ SpFac sp_fac(const SpDev& d, int k) {
+  SpFac L{d.rb_l[0], d.rb_l[1], d.rb_l[2]};
+  if (d.rb_n > 1) {
+    // the global address space spelt out: loaded through the plain pointer under this branch, the factor came as three
+    // flat loads a round after cid / y, behind their wait; as global loads it is issued with them
+    typedef const double __attribute__((address_space(1))) gdouble;
+    gdouble* p = (gdouble*)(d.rb_L + 3 * (size_t)k);
+    L = SpFac{p[0], p[1], p[2]};
+  }
+  return L;
+}
 
 typedef double v4d_t __attribute__((ext_vector_type(4)));
 
@@ -319,9 +353,12 @@ __device__ __forceinline__ void stage_lds(T* dst, const T* src, int n, int tid, 
 // 16 x 16 local Hessian of [J_delta | J_intr | -e] by f64 MFMA SYRK through an LDS tile; then the frame's
 // spline-side blocks (H_vv, H_vtheta, g_v in the curve-value coordinates v, JT folded in) to HBM and the
 // camera-side (theta-theta) sums into the block's partial row.
+// WT (robust terms): a lane scales the two rows of its corner to sqrt(w) L^T [J | -e] before the LDS
+// tile, so the SYRK's [15][15] entry is sum w s and everything after the tile is the unweighted code.
+template <bool WT>
 __device__ __forceinline__ void imu_cc_wave(const SpDev& d, int blk, int lane, double* X);
 
-template <unsigned MM>
+template <unsigned MM, bool WT = false>
 __global__ void __launch_bounds__(512) k_sp_frames(SpDev d) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int N = d.N, C = d.C, nth = blockDim.x, tid = threadIdx.x;
@@ -329,7 +366,7 @@ __global__ void __launch_bounds__(512) k_sp_frames(SpDev d) {
   double* Xw = sm + wave * 64 * XS;
   if ((int)blockIdx.x >= d.nblk_f) {  // the extra blocks: k_sp_imu_cc's work, one of its 64-sample blocks per wave
     const int blk = ((int)blockIdx.x - d.nblk_f) * N + wave;
-    if (blk < d.nblk_ic) imu_cc_wave(d, blk, lane, Xw);
+    if (blk < d.nblk_ic) imu_cc_wave<WT>(d, blk, lane, Xw);
     return;
   }
   double* Hv = sm + N * 64 * XS;   // [N][256]
@@ -497,6 +534,8 @@ __global__ void __launch_bounds__(512) k_sp_frames(SpDev d) {
       if (k < fv.y) {
         const int ci = d.cid[k];
         const double2 yv = d.y[k];
+        SpFac L{1.0, 0.0, 1.0};
+        if constexpr (WT) L = sp_fac(d, k);
         const double X0 = tg[3 * ci], X1 = tg[3 * ci + 1], X2 = tg[3 * ci + 2];
         const double p0 = R[0] * X0 + R[1] * X1 + R[2] * X2 + t[0];
         const double p1 = R[3] * X0 + R[4] * X1 + R[5] * X2 + t[1];
@@ -516,6 +555,16 @@ __global__ void __launch_bounds__(512) k_sp_frames(SpDev d) {
 #pragma unroll
           for (int q = 0; q < 9; ++q) xr[r][6 + q] = (q < nin) ? -Ji[r * KB_MAX_INTR + q] : 0.0;
           xr[r][15] = -(r == 0 ? e0 : e1);
+        }
+        if constexpr (WT) {  // rows -> sqrt(w) L^T rows: r0' = sqrt(w) (l00 r0 + l10 r1), r1' = sqrt(w) l11 r1
+          const double t0 = L.l00 * e0 + L.l10 * e1, t1 = L.l11 * e1;
+          const double sw = sp_sqrt_w(d.rw_kind[0], rb_weight(d.rw_kind[0], d.rw_par[0], fma(t0, t0, t1 * t1)));
+          const double a00 = sw * L.l00, a10 = sw * L.l10, a11 = sw * L.l11;
+#pragma unroll
+          for (int q = 0; q < 16; ++q) {
+            xr[0][q] = a00 * xr[0][q] + a10 * xr[1][q];
+            xr[1][q] = a11 * xr[1][q];
+          }
         }
       }
 #pragma unroll
@@ -740,7 +789,12 @@ __device__ void imu_sample(const SpDev& d, int m, double* e, double* T, double* 
 // One block per cyclic-reduction node i (coefficients 3i..3i+2): D_i (18 x 18), U_i (coupling to node
 // i+1) and R_i = [H_s,theta | g_s] (18 x (C+1)) from the frames and IMU samples whose support touches the
 // node.
+// WT (robust terms): the IMU rows are whitened by the per-sample factors ig sqrt(w_g), ia sqrt(w_a) that imu_cc_wave<true>
+// left in irw (staged with the record, two more doubles per sample) in place of the uniform ig, ia; the record's e
+// arrives scaled.  The frames' blocks are weighted where they are built (k_sp_frames<.., true>).
+template <bool WT = false>
 __global__ void __launch_bounds__(256) k_sp_assemble(SpDev d) {
+  constexpr int RS = WT ? IRS + 2 : IRS;  // LDS stride of a staged record: record | w0 w1 w2 [12] | (ig', ia') | pad
   extern __shared__ __attribute__((aligned(16))) double sm[];
   // XCD-aware node order: blocks are dealt to the 8 XCDs round-robin (block b on XCD b % 8), and a frame or an IMU sample
   // is read by the two neighbouring nodes, so each XCD takes a contiguous run of nodes (node i + 1 on the same L2 as
@@ -833,14 +887,15 @@ __global__ void __launch_bounds__(256) k_sp_assemble(SpDev d) {
   const int wave = tid >> 6, lane = tid & 63;
   v4d_t iacc = {0.0, 0.0, 0.0, 0.0};
   double iac4[3] = {0.0, 0.0, 0.0};
-  double* rec = tj;              // [TCH][IRS]
-  double* P = tj + TCH * IRS;    // [6 PNS][PST]
+  double* rec = tj;              // [TCH][RS]
+  double* P = tj + TCH * RS;     // [6 PNS][PST]
   for (int c0 = ma; c0 < mz; c0 += TCH) {
     const int nt = min(TCH, mz - c0);
     __syncthreads();
     {  // every load in flight before the stores: the IRQ field segments of nt samples, then the chunk's 12 nt weights
-      constexpr int U = (TCH * (IRQ + 12) + 255) / 256;
-      const int nr = IRQ * nt, nall = (IRQ + 12) * nt;
+       // and, WT, its 2 nt whitening factors ig' | ia' (irw)
+      constexpr int U = (TCH * (IRQ + 12 + (WT ? 2 : 0)) + 255) / 256;
+      const int nr = IRQ * nt, nall = (IRQ + 12 + (WT ? 2 : 0)) * nt;
       double v[U];
       int dst[U];
 #pragma unroll
@@ -849,11 +904,15 @@ __global__ void __launch_bounds__(256) k_sp_assemble(SpDev d) {
         if (q < nr) {
           const int a = q / nt, t = q - a * nt;
           v[u] = d.irec[(size_t)a * d.M + c0 + t];
-          dst[u] = t * IRS + a;
-        } else {
+          dst[u] = t * RS + a;
+        } else if (!WT || q < nr + 12 * nt) {
           const int e = q - nr, t = e / 12;
           v[u] = d.iw[(size_t)12 * c0 + e];
-          dst[u] = t * IRS + IRQ + (e - 12 * t);
+          dst[u] = t * RS + IRQ + (e - 12 * t);
+        } else {  // the chunk's ig' [nt] | ia' [nt]
+          const int e = q - nr - 12 * nt, a = e >= nt ? 1 : 0, t = e - a * nt;
+          v[u] = d.irw[(size_t)a * d.M + c0 + t];
+          dst[u] = t * RS + IRQ + 12 + a;
         }
       }
       const int tbv = tid < nt ? d.ib[c0 + tid] : 0;
@@ -875,8 +934,9 @@ __global__ void __launch_bounds__(256) k_sp_assemble(SpDev d) {
         if (item < 48 * PNS) {
           const int tt = item / 48, c = item - 48 * tt;
           const int t = min(s0 + tt, nt - 1);
-          const double* R = rec + t * IRS;
+          const double* R = rec + t * RS;
           const double* w = R + IRQ;
+          const double gi = WT ? R[IRQ + 12] : d.ig, ai = WT ? R[IRQ + 13] : d.ia;
           const int cb = c / 6, cc = c - 6 * cb, jj = k0 + cb - tb[t], j = min(max(jj, 0), 3);
           const bool lo = cc < 3, inj = c < 2 * NB && jj >= 0 && jj <= 3, live = tt < ns;
           const int cr = lo ? cc : cc - 3, ci = min(max(c - 2 * NB, 0), 8), cg = min(max(ci - 6, 0), 2);
@@ -887,12 +947,12 @@ __global__ void __launch_bounds__(256) k_sp_assemble(SpDev d) {
             double vj, vt;
             if (z < 3) {
               const double p1 = wj * R[3 * zr + cr], p2 = w4 * R[9 + 3 * zr + cr];
-              vj = lo ? 0.0 : -(p1 - p2) * d.ig;
-              vt = ci == z ? -d.ig : 0.0;
+              vj = lo ? 0.0 : -(p1 - p2) * gi;
+              vt = ci == z ? -gi : 0.0;
             } else {
               const double p1 = (lo ? w8 : wj) * R[(lo ? 27 : 18) + 3 * zr + cr];
-              vj = lo ? -p1 * d.ia : p1 * d.ia;
-              vt = ci < 3 ? 0.0 : ci < 6 ? (ci - 3 == zr ? -d.ia : 0.0) : R[27 + 3 * zr + cg] * d.ia;
+              vj = lo ? -p1 * ai : p1 * ai;
+              vt = ci < 3 ? 0.0 : ci < 6 ? (ci - 3 == zr ? -ai : 0.0) : R[27 + 3 * zr + cg] * ai;
             }
             const double v = c < 2 * NB ? (inj ? vj : 0.0) : c < 2 * NB + 9 ? vt : c == 2 * NB + 9 ? -R[36 + z] : 0.0;
             P[(6 * tt + z) * PST + c] = live ? v : 0.0;
@@ -1082,6 +1142,10 @@ __global__ void __launch_bounds__(256) k_sp_assemble(SpDev d) {
 // k_sp_imu_cc's work for its block blk (64 samples) on one wave: the samples' records for k_sp_assemble and the partial
 // row [WI] of their theta-theta terms, each entry summed over the 64 samples in order through the wave's 64 x XS LDS
 // tile X, 16 entries at a time.  Run by k_sp_imu_cc and by the extra blocks of k_sp_frames (one launch less per pass).
+// WT (robust terms): the gyro and the accelerometer term of a sample carry the weights w_g(|e_g|^2), w_a(|e_a|^2) of the
+// whitened residuals: the theta-theta row is scaled by them, the record's e by their square roots, and the per-sample
+// whitening factors ig sqrt(w_g), ia sqrt(w_a) go to irw for k_sp_assemble<true>'s panels.
+template <bool WT>
 __device__ __forceinline__ void imu_cc_wave(const SpDev& d, int blk, int lane, double* X) {
   const int m = blk * 64 + lane;
   double e[6] = {0, 0, 0, 0, 0, 0}, Ct[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1091,18 +1155,29 @@ __device__ __forceinline__ void imu_cc_wave(const SpDev& d, int blk, int lane, d
     d.sc[SC_OK] = 1.0;
   }
   double T[27];
+  double wg = 1.0, wa = 1.0;
   if (has) {
     imu_sample(d, m, e, T, Ct);
 #pragma unroll
     for (int q = 0; q < 27; ++q) d.irec[(size_t)q * d.M + m] = T[q];  // field-major: coalesced over the wave
 #pragma unroll
     for (int q = 0; q < 9; ++q) d.irec[(size_t)(27 + q) * d.M + m] = Ct[q];
+    if constexpr (WT) {
+      wg = rb_weight(d.rw_kind[1], d.rw_par[1], e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+      wa = rb_weight(d.rw_kind[2], d.rw_par[2], e[3] * e[3] + e[4] * e[4] + e[5] * e[5]);
+      const double swg = sp_sqrt_w(d.rw_kind[1], wg), swa = sp_sqrt_w(d.rw_kind[2], wa);
 #pragma unroll
-    for (int q = 0; q < 6; ++q) d.irec[(size_t)(36 + q) * d.M + m] = e[q];
+      for (int q = 0; q < 6; ++q) d.irec[(size_t)(36 + q) * d.M + m] = e[q] * (q < 3 ? swg : swa);
+      d.irw[m] = d.ig * swg;
+      d.irw[(size_t)d.M + m] = d.ia * swa;
+    } else {
+#pragma unroll
+      for (int q = 0; q < 6; ++q) d.irec[(size_t)(36 + q) * d.M + m] = e[q];
+    }
   }
   double v[WI];
   // J_theta = [-ig I, 0, 0; 0, -ia I, ia C^T] (rows gyro | accel; columns b_g | b_a | g_w)
-  const double ig2 = d.ig * d.ig, ia2 = d.ia * d.ia;
+  const double ig2 = WT ? d.ig * d.ig * wg : d.ig * d.ig, ia2 = WT ? d.ia * d.ia * wa : d.ia * d.ia;
   int q = 0;
 #pragma unroll
   for (int a = 0; a < 9; ++a)
@@ -1127,9 +1202,17 @@ __device__ __forceinline__ void imu_cc_wave(const SpDev& d, int blk, int lane, d
     } else {
       t = -d.ia * (Ct[0 * 3 + (a - 6)] * e[3] + Ct[1 * 3 + (a - 6)] * e[4] + Ct[2 * 3 + (a - 6)] * e[5]);
     }
+    if constexpr (WT) t *= a < 3 ? wg : wa;
     v[45 + a] = has ? t : 0.0;
   }
-  v[54] = has ? ((e[0] * e[0] + e[1] * e[1]) + (e[2] * e[2] + e[3] * e[3])) + (e[4] * e[4] + e[5] * e[5]) : 0.0;
+  if constexpr (WT) {
+    // w_g s_g + w_a s_a in the shape of the unweighted sum ((w e) e for e e, the same contractions), so that unit
+    // weights return its bits
+    const double g0 = wg * e[0], g1 = wg * e[1], g2 = wg * e[2], a0 = wa * e[3], a1 = wa * e[4], a2 = wa * e[5];
+    v[54] = has ? ((g0 * e[0] + g1 * e[1]) + (g2 * e[2] + a0 * e[3])) + (a1 * e[4] + a2 * e[5]) : 0.0;
+  } else {
+    v[54] = has ? ((e[0] * e[0] + e[1] * e[1]) + (e[2] * e[2] + e[3] * e[3])) + (e[4] * e[4] + e[5] * e[5]) : 0.0;
+  }
 #pragma unroll
   for (int q0 = 0; q0 < WI; q0 += 16) {
 #pragma unroll
@@ -1147,7 +1230,7 @@ __device__ __forceinline__ void imu_cc_wave(const SpDev& d, int blk, int lane, d
 
 __global__ void __launch_bounds__(64) k_sp_imu_cc(SpDev d) {
   __shared__ double X[64 * XS];
-  imu_cc_wave(d, blockIdx.x, threadIdx.x, X);
+  imu_cc_wave<false>(d, blockIdx.x, threadIdx.x, X);
 }
 
 // ---------------------------------------------------------------- k_sp_reduce_cc: H_cc, g_c, cost
@@ -2692,18 +2775,43 @@ __global__ void __launch_bounds__(64) k_sp_update(SpDev d, int apply) {
 }
 
 // ---------------------------------------------------------------- cost (evaluateError)
-template <unsigned MM>
+// WT (robust terms): a corner's chi^2 is w(s) s with s = |L^T e|^2, a sample's w_g s_g + w_a s_a; the unit-weight sums
+// are spelt as the unweighted ones (rb_cost's story), so identity settings return their bits.
+// QUERY (k_sp_weights, kb_sp_get_mestimator_weights only): no sum; s and w of every term of family d.q_term go to d.q_s /
+// d.q_w in upload order.  (One kernel text: as a function shared by two kernels the unweighted instantiation no longer
+// compiled to the instructions it had.)
+template <unsigned MM, bool WT = false, bool QUERY = false>
 __global__ void __launch_bounds__(512) k_sp_cost_frames(SpDev d) {
   __shared__ double red[8];
+  [[maybe_unused]] const int term = d.q_term;
+  [[maybe_unused]] double* const w_out = d.q_w;
+  [[maybe_unused]] double* const s_out = d.q_s;
   const int N = d.N, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, cam = wave;
   if ((int)blockIdx.x >= d.nblk_f) {  // the extra blocks: the IMU samples' chi^2, 64 N samples per block
     const int m = ((int)blockIdx.x - d.nblk_f) * 64 * N + tid;
     double s = 0.0;
+    if constexpr (QUERY) {
+      if (term == KB_SP_TERM_REPROJECTION || m >= d.M) return;
+      double e[6], Ct[9];
+      imu_sample(d, m, e, nullptr, Ct);
+      const bool gy = term == KB_SP_TERM_GYRO;
+      const double sq = gy ? e[0] * e[0] + e[1] * e[1] + e[2] * e[2] : e[3] * e[3] + e[4] * e[4] + e[5] * e[5];
+      s_out[m] = sq;
+      w_out[m] = rb_weight(gy ? d.rw_kind[1] : d.rw_kind[2], gy ? d.rw_par[1] : d.rw_par[2], sq);
+      return;
+    }
     if (m < d.M) {
       double e[6], Ct[9];
       imu_sample(d, m, e, nullptr, Ct);
+      if constexpr (WT) {
+        const double wg = rb_weight(d.rw_kind[1], d.rw_par[1], e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+        const double wa = rb_weight(d.rw_kind[2], d.rw_par[2], e[3] * e[3] + e[4] * e[4] + e[5] * e[5]);
 #pragma unroll
-      for (int r = 0; r < 6; ++r) s += e[r] * e[r];
+        for (int r = 0; r < 6; ++r) s += ((r < 3 ? wg : wa) * e[r]) * e[r];
+      } else {
+#pragma unroll
+        for (int r = 0; r < 6; ++r) s += e[r] * e[r];
+      }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
@@ -2716,6 +2824,8 @@ __global__ void __launch_bounds__(512) k_sp_cost_frames(SpDev d) {
     }
     return;
   }
+  if constexpr (QUERY)
+    if (term != KB_SP_TERM_REPROJECTION) return;
   const double* st = d.state;
   double RA[9], tA[3];
   kb::quat2r(st + d.off_cb, RA);
@@ -2763,6 +2873,8 @@ __global__ void __launch_bounds__(512) k_sp_cost_frames(SpDev d) {
     for (int k = fv.x + lane; k < fv.y; k += 64) {
       const int ci = d.cid[k];
       const double2 yv = d.y[k];
+      SpFac L{1.0, 0.0, 1.0};
+      if constexpr (WT) L = sp_fac(d, k);
       const double* X = d.target + 3 * ci;
       const double p0 = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0];
       const double p1 = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
@@ -2770,9 +2882,22 @@ __global__ void __launch_bounds__(512) k_sp_cost_frames(SpDev d) {
       double u, wv;
       kb::project<MM>(model, intr, p0, p1, p2, u, wv);
       const double e0 = yv.x - u, e1 = yv.y - wv;
-      s += e0 * e0 + e1 * e1;
+      if constexpr (WT) {
+        const double t0 = L.l00 * e0 + L.l10 * e1, t1 = L.l11 * e1;
+        const double sq = fma(t0, t0, t1 * t1);
+        const double w = rb_weight(d.rw_kind[0], d.rw_par[0], sq);
+        if constexpr (QUERY) {
+          s_out[k] = sq;
+          w_out[k] = w;
+        } else {
+          s += (w * t0) * t0 + (w * t1) * t1;  // w s in the shape of e0 e0 + e1 e1: the same contractions
+        }
+      } else {
+        s += e0 * e0 + e1 * e1;
+      }
     }
   }
+  if constexpr (QUERY) return;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   if (lane == 0) red[wave] = s;
@@ -2783,6 +2908,10 @@ __global__ void __launch_bounds__(512) k_sp_cost_frames(SpDev d) {
     d.cpart[blockIdx.x] = t;
   }
 }
+
+// s and w of every term of one family at the current state: k_sp_cost_frames' query instantiation on its grid
+template <unsigned MM>
+constexpr auto k_sp_weights = k_sp_cost_frames<MM, true, true>;
 
 // BSplineMotionError::evaluateErrorImplementation (BSplineMotionError.hpp:62-78): c^T Q c of the current state,
 // one node per lane (c_i^T QD_i c_i + 2 c_i^T QU_i c_(i+1), + the node's own priors' chi^2) -> cpart[nblk_f + nblk_ci +
@@ -3030,8 +3159,13 @@ struct kb_sp_handle {
   bool uploaded = false, built = false, solved = false;
   size_t lds_frames = 0, lds_asm = 0, lds_elim = 0, lds_level = 0, lds_schur = 0, lds_back = 0, lds_back2 = 0;
   bool back2 = true;       // k_sp_back2: two back-substitution strides per launch
+  // the launched instantiations: [0] of an unweighted handle, [1] of a weighted one (pick_weighted)
   const void* fn_frames = nullptr;
   const void* fn_cost = nullptr;
+  const void* fn_asm = nullptr;
+  const void *fns_frames[2] = {}, *fns_cost[2] = {}, *fns_asm[2] = {};
+  size_t ldss_asm[2] = {};
+  const void* fn_weights = nullptr;
   const void* fn_camsolve = nullptr;
   hipGraphExec_t gn_graph = nullptr;
   int gn_graph_n = 0;
@@ -3068,8 +3202,35 @@ struct kb_sp_handle {
 namespace {
 template <unsigned MM>
 void pick_mm(kb_sp_handle* h) {
-  h->fn_frames = (const void*)k_sp_frames<MM>;
-  h->fn_cost = (const void*)k_sp_cost_frames<MM>;
+  h->fns_frames[0] = (const void*)k_sp_frames<MM>;
+  h->fns_cost[0] = (const void*)k_sp_cost_frames<MM>;
+  h->fns_frames[1] = (const void*)k_sp_frames<MM, true>;
+  h->fns_cost[1] = (const void*)k_sp_cost_frames<MM, true>;
+  h->fn_weights = (const void*)k_sp_weights<MM>;
+}
+
+// a handle with an estimator or a corner invR set is weighted
+bool sp_weighted(const kb_sp_handle* h) {
+  const SpDev& d = h->d;
+  return d.rw_kind[0] != KB_MEST_NONE || d.rw_kind[1] != KB_MEST_NONE || d.rw_kind[2] != KB_MEST_NONE || d.rb_n != 0;
+}
+
+// k_sp_assemble<true>'s records are two doubles longer: the one LDS budget that a weighted handle adds to kb_sp_create's
+bool sp_fits_weighted(const kb_sp_handle* h) { return h->ldss_asm[1] <= 160 * 1024; }
+
+// the instantiations the handle launches from now on (an unweighted handle: exactly the ones it always launched), and
+// everything that depended on the old ones dropped: captured passes hold the old SpDev and kernels by value
+void pick_weighted(kb_sp_handle* h) {
+  const int w = sp_weighted(h) ? 1 : 0;
+  h->fn_frames = h->fns_frames[w];
+  h->fn_cost = h->fns_cost[w];
+  h->fn_asm = h->fns_asm[w];
+  h->lds_asm = h->ldss_asm[w];
+  if (h->gn_graph) {
+    hipGraphExecDestroy(h->gn_graph);
+    h->gn_graph = nullptr;
+  }
+  h->built = h->solved = false;
 }
 
 // k_sp_frames' grid: the frame blocks, then ceil(nblk_ic / N) blocks whose N waves each take one of k_sp_imu_cc's
@@ -3082,7 +3243,7 @@ int launch_build(kb_sp_handle* h) {
   // the frames and, in its extra blocks, the IMU samples (k_sp_imu_cc's work: records, partial rows, lambda^2 = 0 of a
   // GN pass)
   KSP_HIP(hipLaunchKernel(h->fn_frames, dim3(frames_grid(h)), dim3(64 * h->N), args, h->lds_frames, h->stream));
-  KSP_HIP(hipLaunchKernel((const void*)k_sp_assemble, dim3(d.n), dim3(256), args, h->lds_asm, h->stream));
+  KSP_HIP(hipLaunchKernel(h->fn_asm, dim3(d.n), dim3(256), args, h->lds_asm, h->stream));
   if (!d.cc_fused) hipLaunchKernelGGL(k_sp_reduce_cc, dim3((d.Wc + 63) / 64), dim3(64 * RW), 0, h->stream, d);
   if (d.cq) hipLaunchKernelGGL(k_sp_mcost_build, dim3(1), dim3(256), 0, h->stream, d);
   return 0;
@@ -3404,17 +3565,26 @@ kb_sp_handle* kb_sp_create(const kb_sp_layout* L) {
     h->back2 = !(ev && std::atoi(ev) == 0);
   }
   h->lds_schur = sizeof(double) * (2 * NB * d.m + d.Ws) + sizeof(short2) * d.Ws;
-  h->lds_asm = sizeof(double) * (2 * NB * NB + NB * d.m + std::max(TCH * IRS + 6 * PNS * PST, TCF * d.FHS));
+  h->fns_asm[0] = (const void*)k_sp_assemble<false>;
+  h->fns_asm[1] = (const void*)k_sp_assemble<true>;
+  for (int w = 0; w < 2; ++w)  // (the weighted records are two doubles longer)
+    h->ldss_asm[w] =
+        sizeof(double) * (2 * NB * NB + NB * d.m + std::max(TCH * (IRS + 2 * w) + 6 * PNS * PST, TCF * d.FHS));
+  d.rb_l[0] = d.rb_l[2] = 1.0;  // invR = I
+  pick_weighted(h);
   h->lds_frames = sizeof(double) * (h->N * 64 * XS + h->N * 256 + 2 * h->N * 36 + 2 * h->N * h->N * 36 +
                                     3 * L->n_target) +
                   sizeof(short2) * d.Wc + sizeof(int) * 3 * d.C;
-  if (h->lds_frames > 160 * 1024 || h->lds_asm > 160 * 1024 || h->lds_schur > 160 * 1024) {
+  if (h->lds_frames > 160 * 1024 || h->ldss_asm[0] > 160 * 1024 || h->lds_schur > 160 * 1024) {
     fail("kb_sp_create: LDS budget exceeded for this rig");
     kb_sp_destroy(h);
     return nullptr;
   }
-  hipFuncSetAttribute(h->fn_frames, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_frames);
-  hipFuncSetAttribute((const void*)k_sp_assemble, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_asm);
+  for (int w = 0; w < 2; ++w) {
+    hipFuncSetAttribute(h->fns_frames[w], hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_frames);
+    if (h->ldss_asm[w] <= 160 * 1024)  // (a rig whose weighted records do not fit stays unweighted: sp_fits_weighted)
+      hipFuncSetAttribute(h->fns_asm[w], hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->ldss_asm[w]);
+  }
   // (the top level's launch may carry the Schur sums' blocks: zsf)
   hipFuncSetAttribute((const void*)k_sp_level<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                       (int)std::max(h->lds_level, h->lds_schur));
@@ -3562,6 +3732,7 @@ int kb_sp_upload(kb_sp_handle* h, int32_t n_frames, const double* frame_time, in
   rc |= h->alloc(&d.mcost, (size_t)h->n);
   rc |= h->alloc(&d.ipart, (size_t)d.nblk_ic * WI);
   rc |= h->alloc(&d.irec, (size_t)IRQ * std::max(M, 1));
+  rc |= h->alloc(&d.irw, 2 * (size_t)std::max(M, 1));
   if (rc) return -1;
   if (n_corners) {
     KSP_HIP(hipMemcpyAsync(dy, y, sizeof(double) * 2 * n_corners, hipMemcpyHostToDevice, h->stream));
@@ -3632,6 +3803,88 @@ int kb_sp_build(kb_sp_handle* h) {
   KSP_HIP(hipGetLastError());
   h->built = true;
   h->solved = false;
+  return 0;
+}
+
+// Robust terms: ErrorTerm::setMEstimatorPolicy per term family and ErrorTermFs::setInvR per corner.  A
+// refused call returns before anything of the handle is touched.
+int kb_sp_set_mestimator(kb_sp_handle* h, int32_t term, const kb_mestimator* m) {
+  if (!h) return fail("kb_sp_set_mestimator: null handle");
+  if (term < KB_SP_TERM_REPROJECTION || term > KB_SP_TERM_ACCEL)
+    return fail("kb_sp_set_mestimator: unknown term family (KB_SP_TERM_REPROJECTION, _GYRO or _ACCEL)");
+  const int kind = m ? m->kind : KB_MEST_NONE;
+  if (kind < KB_MEST_NONE || kind > KB_MEST_BLAKE_ZISSERMAN) return fail("kb_sp_set_mestimator: unknown estimator kind");
+  if (kind != KB_MEST_NONE && !(std::isfinite(m->param) && m->param > 0.0))
+    return fail("kb_sp_set_mestimator: the estimator parameter must be positive and finite");
+  if (kind != KB_MEST_NONE && !sp_fits_weighted(h))
+    return fail("kb_sp_set_mestimator: the k_sp_assemble LDS budget is exceeded for this rig");
+  KSP_HIP(hipSetDevice(h->device));
+  h->d.rw_kind[term] = kind;
+  h->d.rw_par[term] = kind != KB_MEST_NONE ? m->param : 0.0;
+  pick_weighted(h);
+  return 0;
+}
+
+int kb_sp_set_corner_invR(kb_sp_handle* h, const double* invR3, int32_t n) {
+  if (!h) return fail("kb_sp_set_corner_invR: null handle");
+  if (!invR3) n = 0;
+  if (n > 1 && !h->uploaded) return fail("kb_sp_set_corner_invR: a per-corner invR needs kb_sp_upload first");
+  if (n != 0 && n != 1 && n != h->NCo) return fail("kb_sp_set_corner_invR: n must be 0, 1 or the number of corners");
+  std::vector<double> L(3 * (size_t)std::max(n, 0));
+  for (int k = 0; k < n; ++k) {  // lower Cholesky factor of [[a, b], [b, c]]
+    const double a = invR3[3 * k], b = invR3[3 * k + 1], c = invR3[3 * k + 2];
+    const double l00 = std::sqrt(a), l10 = b / l00, r = c - l10 * l10;
+    if (!(std::isfinite(a) && std::isfinite(b) && std::isfinite(c) && a > 0.0 && r > 0.0 && std::isfinite(l10)))
+      return fail("kb_sp_set_corner_invR: invR of corner " + std::to_string(k) + " is not positive definite");
+    L[3 * k] = l00;
+    L[3 * k + 1] = l10;
+    L[3 * k + 2] = std::sqrt(r);
+  }
+  if (n != 0 && !sp_fits_weighted(h))
+    return fail("kb_sp_set_corner_invR: the k_sp_assemble LDS budget is exceeded for this rig");
+  KSP_HIP(hipSetDevice(h->device));
+  SpDev& d = h->d;
+  if (n > 1) {
+    double* dl = const_cast<double*>(d.rb_L);
+    if (!dl && h->alloc(&dl, 3 * (size_t)n)) return -1;  // (one upload per handle: the corner count is fixed)
+    if (hipMemcpyAsync(dl, L.data(), sizeof(double) * L.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess) {
+      if (!d.rb_L) h->release(dl);
+      return fail("kb_sp_set_corner_invR: upload of the factors failed");
+    }
+    d.rb_L = dl;
+  }
+  d.rb_n = n;
+  d.rb_l[0] = n == 1 ? L[0] : 1.0;
+  d.rb_l[1] = n == 1 ? L[1] : 0.0;
+  d.rb_l[2] = n == 1 ? L[2] : 1.0;
+  pick_weighted(h);
+  return 0;
+}
+
+int kb_sp_get_mestimator_weights(kb_sp_handle* h, int32_t term, double* w_out, double* s_out) {
+  if (!h || !w_out) return fail("kb_sp_get_mestimator_weights: null");
+  if (term < KB_SP_TERM_REPROJECTION || term > KB_SP_TERM_ACCEL)
+    return fail("kb_sp_get_mestimator_weights: unknown term family");
+  if (!h->uploaded) return fail("kb_sp_get_mestimator_weights: upload observations first");
+  KSP_HIP(hipSetDevice(h->device));
+  const size_t n = term == KB_SP_TERM_REPROJECTION ? (size_t)h->NCo : (size_t)h->M;
+  if (n == 0) return 0;
+  double* ws = nullptr;
+  if (h->alloc(&ws, 2 * n)) return -1;
+  SpDev d = h->d;
+  double* so = ws + n;
+  d.q_term = term;
+  d.q_w = ws;
+  d.q_s = so;
+  void* args[] = {&d};
+  hipError_t e = hipLaunchKernel(h->fn_weights, dim3(d.nblk_f + d.nblk_ci), dim3(64 * h->N), args, 0, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(w_out, ws, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && s_out) e = hipMemcpyAsync(s_out, so, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream);
+  const hipError_t es = hipStreamSynchronize(h->stream);
+  h->release(ws);
+  if (e != hipSuccess || es != hipSuccess)
+    return fail(std::string("kb_sp_get_mestimator_weights: ") + hipGetErrorString(e != hipSuccess ? e : es));
   return 0;
 }
 
@@ -4071,7 +4324,7 @@ int kb_sp_assemble_stats(kb_sp_handle* h, int32_t n, double* ms, double* bytes) 
     hipLaunchKernelGGL(k_sp_set_lam, dim3(1), dim3(64), 0, h->stream, d, 0.0);
     KSP_HIP(hipLaunchKernel(h->fn_frames, dim3(frames_grid(h)), dim3(64 * h->N), args, h->lds_frames, h->stream));
     KSP_HIP(hipEventRecord(e0, h->stream));
-    KSP_HIP(hipLaunchKernel((const void*)k_sp_assemble, dim3(d.n), dim3(256), args, h->lds_asm, h->stream));
+    KSP_HIP(hipLaunchKernel(h->fn_asm, dim3(d.n), dim3(256), args, h->lds_asm, h->stream));
     KSP_HIP(hipEventRecord(e1, h->stream));
     KSP_HIP(hipStreamSynchronize(h->stream));
     float t = 0.0f;
@@ -4104,7 +4357,7 @@ int kb_sp_kernel_stats(kb_sp_handle* h, int32_t n, double* ms_out6, double* fram
     KSP_HIP(hipEventRecord(ev[0], h->stream));
     KSP_HIP(hipLaunchKernel(h->fn_frames, dim3(frames_grid(h)), dim3(64 * h->N), args, h->lds_frames, h->stream));
     KSP_HIP(hipEventRecord(ev[1], h->stream));
-    KSP_HIP(hipLaunchKernel((const void*)k_sp_assemble, dim3(d.n), dim3(256), args, h->lds_asm, h->stream));
+    KSP_HIP(hipLaunchKernel(h->fn_asm, dim3(d.n), dim3(256), args, h->lds_asm, h->stream));
     hipLaunchKernelGGL(k_sp_reduce_cc, dim3((d.Wc + 63) / 64), dim3(64 * RW), 0, h->stream, d);
     if (d.cq) hipLaunchKernelGGL(k_sp_mcost_build, dim3(1), dim3(256), 0, h->stream, d);
     KSP_HIP(hipEventRecord(ev[2], h->stream));

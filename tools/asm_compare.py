@@ -9,7 +9,11 @@ of a parameter added later (`--drop-default ', false>'` turns `k_buildp<7, true,
 `k_buildp<7, true, 1u, 12>`) is dropped from the names of the second file, and from the mangled names inside both
 streams, so that a new defaulted template parameter does not count as a difference.
 
-  python tools/asm_compare.py parent.s new.s [--drop-default ', false>'] [--list]
+--kernarg-shift SIZE:DELTA: the struct every kernel takes by value grew by DELTA bytes at its end (no field moved), so
+the arguments after it and the hidden ones sit DELTA bytes later; their scalar loads (and the s_add_u32 that forms the
+hidden arguments' address) are compared at the old offsets.
+
+  python tools/asm_compare.py parent.s new.s [--drop-default ', false>'] [--kernarg-shift 0x600:0x70] [--list]
 prints: functions in each, identical, different, only in one; exit status 1 when an instruction stream differs.
 """
 import argparse
@@ -54,17 +58,34 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("a")
     ap.add_argument("b")
-    ap.add_argument("--drop-default", default=None, help="demangled suffix of the second file's names to drop")
+    ap.add_argument("--drop-default", action="append", default=[],
+                    help="demangled suffix of the second file's names to drop (repeatable; '<false>' drops a whole "
+                         "argument list: a kernel that became a template)")
     ap.add_argument("--list", action="store_true", help="name every function, not only the counts")
+    ap.add_argument("--kernarg-shift", default=None, metavar="SIZE:DELTA",
+                    help="the by-value struct every kernel takes first grew from SIZE by DELTA bytes at its end: scalar "
+                         "loads of the second file at offsets >= SIZE + DELTA (the arguments after it and the hidden "
+                         "ones) are compared at offset - DELTA")
     a = ap.parse_args()
     fa, fb = functions(a.a), functions(a.b)
+    if a.kernarg_shift:
+        size, delta = (int(x, 0) for x in a.kernarg_shift.split(":"))
+
+        def unshift(m):
+            off = int(m.group(2), 16)
+            hit = off >= size + delta and (m.group(1).startswith("s_load") or off < size + delta + 0x100)
+            return m.group(1) + ("0x%x" % (off - delta) if hit else m.group(2))
+        for s in fb:
+            fb[s] = [re.sub(r"^((?:s_load_\w+ .*|s_add_u32 s\d+, s\d+), )(0x[0-9a-f]+)$", unshift, t) for t in fb[s]]
     da, db = demangle(list(fa)), demangle(list(fb))
     rename = {}  # mangled name of the second file -> the first file's
     by_dem_a = {v: k for k, v in da.items()}
-    if a.drop_default:
-        for s, dn in db.items():
-            if a.drop_default in dn:
-                short = dn.replace(a.drop_default, ">" if a.drop_default.endswith(">") else "")
+    for dd in a.drop_default:
+        for s, dn in list(db.items()):
+            if dd in dn:
+                short = dn.replace(dd, "" if dd.startswith("<") else ">" if dd.endswith(">") else "")
+                if dd.startswith("<") and short.startswith("void "):  # a plain function's name has no return type
+                    short = short[5:]
                 if short in by_dem_a:
                     rename[s] = by_dem_a[short]
                     db[s] = short
