@@ -380,6 +380,11 @@ int kb_build_kernel_stats(kb_handle* h, double* avg_ms, double* bytes_per_launch
 int kb_gn_pass_times(kb_handle* h, int32_t n, double* pass_ms, double* build_ms);
 /* Name of the build kernel this handle launches ("k_buildp" or "k_build") into buf (NUL-terminated). */
 int kb_build_kernel_name(kb_handle* h, char* buf, int32_t cap);
+/* 1 when this handle's k_buildp launches carry the per-view table (each view's rigid transform and chain computed
+ * once per block into LDS instead of once per frame by every lane), 0 when they do not: the handle builds with
+ * k_build, the table does not fit the block's LDS at the current frame count, or KB_BUILDP_VIEWTAB=0 was set at
+ * kb_create.  Read-only; the value can change with kb_append_frames / kb_drop_last_frames and the robust setters. */
+int kb_build_viewtab(kb_handle* h);
 
 /* Multi-GPU (frame sharding): each rank's handle holds its own frames;
  * the camera-block [S | b] and the cost/step statistics are all-reduced over RCCL once

@@ -58,6 +58,33 @@ inline bool build_fits(const Rig& r, bool pipe, int F) {
   return build_lds(r, pipe, gframes(pipe, r.bpc, F), nullptr) + (pipe ? kBuildpStaticLds : 0) <= kLdsLimit;
 }
 
+// k_buildp's per-view table: one record per (frame of the block, camera) holding the view's
+// rigid transform and chain, R (9) | t (3) | G (36, row-major), filled once per block and read by the view waves
+// instead of being recomputed per frame.  It lies behind every other region of the dynamic LDS, so build_lds and
+// build_fits do not know it: the launch asks for viewtab_total when viewtab_fits, else for build_lds as before.
+// The record stride is odd in doubles: at 48 every lane of a one-view-per-lane store would hit the same bank pair.
+constexpr int kViewtabRec = 48;
+constexpr int kViewtabStride = 49;
+
+// bytes of the table at `gf` frames per block
+inline size_t viewtab_lds(const Rig& r, int gf) { return sizeof(double) * (size_t)kViewtabStride * gf * r.N; }
+
+// dynamic LDS (bytes) of a k_buildp launch that carries the table
+inline size_t viewtab_total(const Rig& r, int gf) { return build_lds(r, true, gf, nullptr) + viewtab_lds(r, gf); }
+
+// the table fits beside the rest at F frames: dynamic and static LDS within a block's share of the CU (the whole
+// LDS at one block per CU, half of it for the rigs that run two, which must stay co-resident)
+inline bool viewtab_fits(const Rig& r, bool pipe, int F) {
+  if (!pipe) return false;
+  const int bpc = r.bpc > 1 ? r.bpc : 1;
+  return viewtab_total(r, gframes(true, bpc, F)) + kBuildpStaticLds <= kLdsLimit / bpc;
+}
+
+// the table pays from two frames per block on: the fill and its barrier cost a block about what one frame's head
+// gives back (0.4 us against 0.3 to 0.45 us per frame at configs[3], profiles/r16/), so a one-frame block only loses
+constexpr int kViewtabMinFrames = 2;
+inline bool viewtab_pays(int gf) { return gf >= kViewtabMinFrames; }
+
 // Robust terms (kb_set_mestimator / kb_set_corner_invR / kb_set_robust_build): the kernel a handle builds with.
 // `pipe0` is kb_create's choice for the unweighted handle; a weighted handle keeps it only in pipe mode
 // (KB_ROBUST_BUILD_PIPE: the weighted k_buildp), otherwise it builds with k_build.

@@ -20,14 +20,21 @@ constexpr unsigned kTuMm[9] = {1u << KB_PINHOLE_RADTAN, 1u << KB_OMNI_RADTAN, 1u
 constexpr unsigned MM = kTuMm[KB_TU_ID];
 
 // mb: Schur tiles per wave of k_build (1 | 4 | 7), or per frame wave of k_buildp (5: 2 frame waves | 7: 4) when pipe
-template <bool GN>
-const void* build_fn(int mb, bool pipe, bool wide) {
+// vt: the k_buildp instantiation that carries the per-view table (the host found room for it)
+template <bool GN, bool VT>
+const void* buildp_fn(int mb, bool wide) {
   using namespace kb;
   constexpr int MWN = kBuildpMaxCams + 4;
   if constexpr (__builtin_popcount(MM) >= 2) {  // multi-model view roles: the spill-free 8-wave variant
-    if (pipe && wide) return mb == 5 ? (const void*)k_buildp<5, GN, MM, 8> : (const void*)k_buildp<7, GN, MM, 8>;
+    if (wide)
+      return mb == 5 ? (const void*)k_buildp<5, GN, MM, 8, false, VT> : (const void*)k_buildp<7, GN, MM, 8, false, VT>;
   }
-  if (pipe) return mb == 5 ? (const void*)k_buildp<5, GN, MM, MWN> : (const void*)k_buildp<7, GN, MM, MWN>;
+  return mb == 5 ? (const void*)k_buildp<5, GN, MM, MWN, false, VT> : (const void*)k_buildp<7, GN, MM, MWN, false, VT>;
+}
+template <bool GN>
+const void* build_fn(int mb, bool pipe, bool wide, bool vt) {
+  using namespace kb;
+  if (pipe) return vt ? buildp_fn<GN, true>(mb, wide) : buildp_fn<GN, false>(mb, wide);
   return mb == 1 ? (const void*)k_build<1, GN, MM> : mb == 4 ? (const void*)k_build<4, GN, MM>
                                                              : (const void*)k_build<7, GN, MM>;
 }
@@ -44,28 +51,33 @@ const void* build_fn_w(int mb) {
 #if defined(KB_CORNER_OLD) || defined(KB_SYRK16) || defined(KB_CORNER_CLAMP) || defined(KB_CORNER_NOZERO) || \
     defined(KB_DIAG_NOPROJ) || defined(KB_DIAG_NOSYRK)
 template <bool GN>
-const void* build_fn_pw(int, bool) {
+const void* build_fn_pw(int, bool, bool) {
   return nullptr;
 }
 #else
-template <bool GN>
-const void* build_fn_pw(int mb, bool wide) {
+template <bool GN, bool VT>
+const void* buildp_fn_w(int mb, bool wide) {
   using namespace kb;
   constexpr int MWN = kBuildpMaxCams + 4;
   if constexpr (__builtin_popcount(MM) >= 2) {
-    if (wide) return mb == 5 ? (const void*)k_buildp<5, GN, MM, 8, true> : (const void*)k_buildp<7, GN, MM, 8, true>;
+    if (wide)
+      return mb == 5 ? (const void*)k_buildp<5, GN, MM, 8, true, VT> : (const void*)k_buildp<7, GN, MM, 8, true, VT>;
   }
-  return mb == 5 ? (const void*)k_buildp<5, GN, MM, MWN, true> : (const void*)k_buildp<7, GN, MM, MWN, true>;
+  return mb == 5 ? (const void*)k_buildp<5, GN, MM, MWN, true, VT> : (const void*)k_buildp<7, GN, MM, MWN, true, VT>;
+}
+template <bool GN>
+const void* build_fn_pw(int mb, bool wide, bool vt) {
+  return vt ? buildp_fn_w<GN, true>(mb, wide) : buildp_fn_w<GN, false>(mb, wide);
 }
 #endif
 }  // namespace
 
 #define KB_CAT2(a, b) a##b
 #define KB_CAT(a, b) KB_CAT2(a, b)
-const void* KB_CAT(kb_build_fn_, KB_TU_ID)(bool gn, int mb, bool pipe, bool wide) {
-  return gn ? build_fn<true>(mb, pipe, wide) : build_fn<false>(mb, pipe, wide);
+const void* KB_CAT(kb_build_fn_, KB_TU_ID)(bool gn, int mb, bool pipe, bool wide, bool vt) {
+  return gn ? build_fn<true>(mb, pipe, wide, vt) : build_fn<false>(mb, pipe, wide, vt);
 }
 const void* KB_CAT(kb_build_fn_w_, KB_TU_ID)(int mb) { return build_fn_w(mb); }
-const void* KB_CAT(kb_build_fn_pw_, KB_TU_ID)(bool gn, int mb, bool wide) {
-  return gn ? build_fn_pw<true>(mb, wide) : build_fn_pw<false>(mb, wide);
+const void* KB_CAT(kb_build_fn_pw_, KB_TU_ID)(bool gn, int mb, bool wide, bool vt) {
+  return gn ? build_fn_pw<true>(mb, wide, vt) : build_fn_pw<false>(mb, wide, vt);
 }

@@ -135,6 +135,8 @@ struct kb_handle {
   bool xar_failed = false;        // a k_xar wait of this rank timed out (comm_check): agreed on at the next loop start
   double* xar_agree_buf = nullptr;  // [2]: this rank's failure flag | the sum over the ranks
   bool buildp_wide = false;  // k_buildp<.., MW = 8> (multi-model rigs with <= 8 waves per block)
+  bool viewtab_allowed = true;  // k_buildp's per-view LDS table where it fits (KB_BUILDP_VIEWTAB=0: never)
+  bool viewtab = false;         // the handle launches the k_buildp<.., VT = true> instantiations (build_lds decides)
   // robust terms (kb_set_mestimator / kb_set_corner_invR): the settings themselves live in d.rb_*
   bool build_pipe0 = false;  // build_pipe of the unweighted handle (a weighted one takes k_build unless rb_build is PIPE)
   int rb_build = KB_ROBUST_BUILD_GENERAL;  // kb_set_robust_build: the build kernel of the weighted handle
@@ -222,12 +224,12 @@ struct kb_handle {
 };
 
 // The build kernels of each camera-model set live in their own translation unit (kb_build_tu.hip, -DKB_TU_ID=id):
-// kb_build_fn_<id>(gn, mb, pipe, wide) returns the k_build / k_buildp instantiation (mb: Schur tiles per wave of
+// kb_build_fn_<id>(gn, mb, pipe, wide, vt) returns the k_build / k_buildp instantiation (mb: Schur tiles per wave of
 // k_build 1 | 4 | 7, or per frame wave of k_buildp 5 | 7).
 #define KB_BUILD_TU_DECL(id)                                            \
-  const void* kb_build_fn_##id(bool gn, int mb, bool pipe, bool wide); \
-  const void* kb_build_fn_w_##id(int mb);                              \
-  const void* kb_build_fn_pw_##id(bool gn, int mb, bool wide);
+  const void* kb_build_fn_##id(bool gn, int mb, bool pipe, bool wide, bool vt); \
+  const void* kb_build_fn_w_##id(int mb);                                       \
+  const void* kb_build_fn_pw_##id(bool gn, int mb, bool wide, bool vt);
 KB_BUILD_TU_DECL(0)
 KB_BUILD_TU_DECL(1)
 KB_BUILD_TU_DECL(2)
@@ -240,17 +242,17 @@ KB_BUILD_TU_DECL(8)
 
 // Build kernel for the rig's camera-model set `mm` (bit m = model m present).
 template <bool GN>
-static const void* pick_build(int mb, unsigned mm, bool pipe, bool wide) {
+static const void* pick_build(int mb, unsigned mm, bool pipe, bool wide, bool vt) {
   switch (mm) {
-    case 1u << KB_PINHOLE_RADTAN: return kb_build_fn_0(GN, mb, pipe, wide);
-    case 1u << KB_OMNI_RADTAN: return kb_build_fn_1(GN, mb, pipe, wide);
-    case 1u << KB_EUCM: return kb_build_fn_2(GN, mb, pipe, wide);
-    case 1u << KB_OMNI: return kb_build_fn_3(GN, mb, pipe, wide);
-    case 1u << KB_DS: return kb_build_fn_4(GN, mb, pipe, wide);
-    case 1u << KB_PINHOLE_EQUI: return kb_build_fn_5(GN, mb, pipe, wide);
-    case 1u << KB_PINHOLE_FOV: return kb_build_fn_6(GN, mb, pipe, wide);
-    case (1u << KB_OMNI_RADTAN) | (1u << KB_EUCM): return kb_build_fn_7(GN, mb, pipe, wide);
-    default: return kb_build_fn_8(GN, mb, pipe, wide);
+    case 1u << KB_PINHOLE_RADTAN: return kb_build_fn_0(GN, mb, pipe, wide, vt);
+    case 1u << KB_OMNI_RADTAN: return kb_build_fn_1(GN, mb, pipe, wide, vt);
+    case 1u << KB_EUCM: return kb_build_fn_2(GN, mb, pipe, wide, vt);
+    case 1u << KB_OMNI: return kb_build_fn_3(GN, mb, pipe, wide, vt);
+    case 1u << KB_DS: return kb_build_fn_4(GN, mb, pipe, wide, vt);
+    case 1u << KB_PINHOLE_EQUI: return kb_build_fn_5(GN, mb, pipe, wide, vt);
+    case 1u << KB_PINHOLE_FOV: return kb_build_fn_6(GN, mb, pipe, wide, vt);
+    case (1u << KB_OMNI_RADTAN) | (1u << KB_EUCM): return kb_build_fn_7(GN, mb, pipe, wide, vt);
+    default: return kb_build_fn_8(GN, mb, pipe, wide, vt);
   }
 }
 
@@ -272,17 +274,17 @@ static const void* pick_build_w(int mb, unsigned mm) {
 // The weighted pipelined build kernel k_buildp<mb, GN, mm, MW, WT = true> (robust terms, KB_ROBUST_BUILD_PIPE); null
 // in a measurement variant of the library whose k_buildp carries no weights.
 template <bool GN>
-static const void* pick_build_pw(int mb, unsigned mm, bool wide) {
+static const void* pick_build_pw(int mb, unsigned mm, bool wide, bool vt) {
   switch (mm) {
-    case 1u << KB_PINHOLE_RADTAN: return kb_build_fn_pw_0(GN, mb, wide);
-    case 1u << KB_OMNI_RADTAN: return kb_build_fn_pw_1(GN, mb, wide);
-    case 1u << KB_EUCM: return kb_build_fn_pw_2(GN, mb, wide);
-    case 1u << KB_OMNI: return kb_build_fn_pw_3(GN, mb, wide);
-    case 1u << KB_DS: return kb_build_fn_pw_4(GN, mb, wide);
-    case 1u << KB_PINHOLE_EQUI: return kb_build_fn_pw_5(GN, mb, wide);
-    case 1u << KB_PINHOLE_FOV: return kb_build_fn_pw_6(GN, mb, wide);
-    case (1u << KB_OMNI_RADTAN) | (1u << KB_EUCM): return kb_build_fn_pw_7(GN, mb, wide);
-    default: return kb_build_fn_pw_8(GN, mb, wide);
+    case 1u << KB_PINHOLE_RADTAN: return kb_build_fn_pw_0(GN, mb, wide, vt);
+    case 1u << KB_OMNI_RADTAN: return kb_build_fn_pw_1(GN, mb, wide, vt);
+    case 1u << KB_EUCM: return kb_build_fn_pw_2(GN, mb, wide, vt);
+    case 1u << KB_OMNI: return kb_build_fn_pw_3(GN, mb, wide, vt);
+    case 1u << KB_DS: return kb_build_fn_pw_4(GN, mb, wide, vt);
+    case 1u << KB_PINHOLE_EQUI: return kb_build_fn_pw_5(GN, mb, wide, vt);
+    case 1u << KB_PINHOLE_FOV: return kb_build_fn_pw_6(GN, mb, wide, vt);
+    case (1u << KB_OMNI_RADTAN) | (1u << KB_EUCM): return kb_build_fn_pw_7(GN, mb, wide, vt);
+    default: return kb_build_fn_pw_8(GN, mb, wide, vt);
   }
 }
 
@@ -328,10 +330,17 @@ static void set_frame_counts(kb_handle* h) {
 // (the arithmetic is kb_build_layout.h's)
 using kb_blay::kBuildpStaticLds;
 static_assert(kb_blay::kXS == XS && kb_blay::kTargetLds == kTargetLds, "kb_build_layout.h: kernel constants");
+static_assert(kb_blay::kViewtabStride == kVtStride && kb_blay::kViewtabRec <= kVtStride, "kb_build_layout.h: view table");
 static kb_blay::Rig layout_rig(const kb_handle* h) { return {h->N, h->C, h->K, h->d.wpb, h->bpc}; }
 
+// k_buildp's per-view table (kb_build_layout.h) rides behind the rest where it fits at the handle's frame count,
+// decided anew wherever the frames per block can change (kb_create, relayout: kb_append_frames,
+// kb_drop_last_frames and the robust setters); KB_BUILDP_VIEWTAB=0 (read at kb_create) keeps it off
 static size_t build_lds(kb_handle* h) {
-  return kb_blay::build_lds(layout_rig(h), h->build_pipe, h->d.gframes, &h->d.bp_tg);
+  const kb_blay::Rig r = layout_rig(h);
+  const size_t base = kb_blay::build_lds(r, h->build_pipe, h->d.gframes, &h->d.bp_tg);
+  h->viewtab = h->viewtab_allowed && kb_blay::viewtab_fits(r, h->build_pipe, h->F) && kb_blay::viewtab_pays(h->d.gframes);
+  return h->viewtab ? kb_blay::viewtab_total(r, h->d.gframes) : base;
 }
 
 // the build kernel's LDS fits at F frames (checked before kb_append_frames / kb_drop_last_frames change anything)
@@ -433,6 +442,8 @@ static int regrow(kb_handle* h, T** p, size_t n_new, size_t keep) {
   return 0;
 }
 
+static void set_build_kernels(kb_handle* h);
+
 // the frame-count-dependent launch state after kb_append_frames / kb_drop_last_frames: LDS of the build kernel,
 // captured graphs (their kernel arguments hold the old layout), prepared loops and the per-call system
 // (the callers check build_lds_fits for the new frame count before they change the handle)
@@ -442,6 +453,7 @@ static int relayout(kb_handle* h) {
   h->sys_valid = false;
   set_frame_counts(h);
   h->lds_build = build_lds(h);
+  set_build_kernels(h);  // the per-view table comes and goes with the frames per block: its instantiations with it
   // one partial row per build block: fewer frames can mean more blocks (one frame per block below 256 bpc frames,
   // several above), so a dropped batch may need more rows than the handle was created with
   if (h->d.nblk > h->part_rows) {
@@ -464,17 +476,18 @@ static void set_build_kernels(kb_handle* h) {
   h->mb = h->build_pipe ? ((ntiles + 1) / 2 <= 5 ? 5 : 7) : tb <= 1 ? 1 : tb <= 4 ? 4 : 7;
   unsigned mm = 0;
   for (int i = 0; i < h->N; ++i) mm |= 1u << d.model[i];
+  const bool vt = h->build_pipe && h->viewtab;  // the instantiations that carry the per-view table (build_lds decides)
   if (weighted(h) && h->build_pipe) {
-    h->fn_build = pick_build_pw<false>(h->mb, mm, h->buildp_wide);
-    h->fn_build_gn = pick_build_pw<true>(h->mb, mm, h->buildp_wide);
+    h->fn_build = pick_build_pw<false>(h->mb, mm, h->buildp_wide, vt);
+    h->fn_build_gn = pick_build_pw<true>(h->mb, mm, h->buildp_wide, vt);
     return;
   }
   if (weighted(h)) {
     h->fn_build = h->fn_build_gn = pick_build_w(h->mb, mm);
     return;
   }
-  h->fn_build = pick_build<false>(h->mb, mm, h->build_pipe, h->buildp_wide);
-  h->fn_build_gn = pick_build<true>(h->mb, mm, h->build_pipe, h->buildp_wide);
+  h->fn_build = pick_build<false>(h->mb, mm, h->build_pipe, h->buildp_wide, vt);
+  h->fn_build_gn = pick_build<true>(h->mb, mm, h->build_pipe, h->buildp_wide, vt);
 }
 
 // A change of the robust settings: a weighted handle builds with k_build (the layout KB_BUILD_PIPE=0 gives: frames
@@ -597,6 +610,7 @@ kb_handle* kb_create(const kb_layout* L) {
     if (const char* e = std::getenv("KB_BUILDP_WIDE")) h->buildp_wide = h->buildp_wide && std::atoi(e) != 0;
     h->bpc = (h->N + nf <= 6 && !h->buildp_wide) ? 2 : 1;
   }
+  if (const char* e = std::getenv("KB_BUILDP_VIEWTAB")) h->viewtab_allowed = std::atoi(e) != 0;
   set_frame_counts(h);
   h->F_cap = h->F;
   d.W = h->W;
@@ -1259,7 +1273,7 @@ int kb_set_robust_build(kb_handle* h, int32_t mode) {
                   "KB_BUILD_PIPE=0); the weighted k_buildp needs a rig that kb_create gave k_buildp");
     unsigned mm = 0;
     for (int i = 0; i < h->N; ++i) mm |= 1u << h->d.model[i];
-    if (!pick_build_pw<false>(5, mm, h->buildp_wide))
+    if (!pick_build_pw<false>(5, mm, h->buildp_wide, false))
       return fail("kb_set_robust_build: this measurement variant of the library has no weighted k_buildp");
   }
   if (mode == h->rb_build) return 0;
@@ -2650,6 +2664,11 @@ int kb_build_kernel_name(kb_handle* h, char* buf, int32_t cap) {
   if (!h || !buf || cap < 1) return fail("kb_build_kernel_name: bad args");
   std::snprintf(buf, cap, "%s", h->build_pipe ? "k_buildp" : "k_build");
   return 0;
+}
+
+int kb_build_viewtab(kb_handle* h) {
+  if (!h) return fail("kb_build_viewtab: bad args");
+  return h->build_pipe && h->viewtab ? 1 : 0;
 }
 
 int kb_comm_get_unique_id(void* out) {

@@ -1353,6 +1353,8 @@ __global__ void __launch_bounds__(512) k_build(KbDev d, int gate, int fuse) {
 // the baseline columns (per-camera products summed over cameras).
 // ---------------------------------------------------------------------------------------------
 constexpr int kBuildpMaxCams = 8;
+// k_buildp's per-view table: record stride in doubles, R (9) | t (3) | G (36) | pad (kb_build_layout.h kViewtabStride)
+constexpr int kVtStride = 49;
 
 // frame waves of k_buildp: the Schur tiles per frame wave TT picks them (<= 5 tiles: 2 waves, else 4: one frame wave
 // per SIMD beside its two view waves)
@@ -1443,7 +1445,11 @@ constexpr bool buildp_view_cic_once() {
 // WT: robust terms as in k_build<.., WT = true> (kb_set_robust_build(h, KB_ROBUST_BUILD_PIPE)): a view lane scales the
 //     two rows of its corner by sqrt(w) L^T before the LDS tile; the per-corner factor (rb_n > 1) travels with cid / y
 //     at each of their three load sites.  With GNF the candidate cost of the fused pass, H[15][15], is sum w s.
-template <int TT, bool GNF, unsigned MM, int MW, bool WT = false>
+// VT: the block carries the per-view table (the host launches these instantiations with the table's LDS behind
+//     the rest, kb_capi.hip build_lds): the view loop reads each view's transform and chain instead of computing them, and the
+//     per-frame computation is not compiled into it (as a run-time branch it kept its registers and cost the
+//     table-less path 1.6 % at configs[3], profiles/r16/).
+template <int TT, bool GNF, unsigned MM, int MW, bool WT = false, bool VT = false>
 __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse) {
   if constexpr (!buildp_vgpr_acc<MM, MW, WT>()) KB_MFMA_AGPR();
   pass_stamp(d);
@@ -1555,6 +1561,7 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
   }
   const int done = __builtin_amdgcn_readfirstlane(c_done), dob = __builtin_amdgcn_readfirstlane(c_dob);
   const int cur = __builtin_amdgcn_readfirstlane(c_cur);
+  if (wave == 0) KB_TSB(d, 18);
   const double lam = gate ? c_lam : d.host_lambda;
   int2 fv;
   fv.x = __builtin_amdgcn_readfirstlane(fvl.x);
@@ -1574,6 +1581,11 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
   // the view outputs are double-buffered: frame f's in VB (f - f0 even) or VB1 (odd), so that the frame waves sum
   // frame f - 1 while the view waves run frame f
   double* VB1 = fpl + 8 * d.gframes;
+  // the per-view table (behind every other region, outside the expanded-partials overlay at the head of sm):
+  // [G][N] records of T_cam_w = (R | t) and the chain G of view (frame, camera), filled once below where the host
+  // found room for it (the VT instantiations); the view waves then read what they would otherwise recompute every frame
+  double* VTl = VB1 + VBS;
+  constexpr bool vt = VT;
   int cidn;  // view waves: lane = corner of a 64-corner pass
   double2 yn;
   RbFac Ln = {1.0, 0.0, 1.0};
@@ -1651,6 +1663,29 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
     xcnt = 0;
     fcnt = 0;
   }
+  if (wave == 0) KB_TSB(d, 19);
+  if constexpr (vt) {  // every thread takes the barrier
+    __syncthreads();  // the chains (cst) and the staged poses (fpl) of every wave, before the fill reads them
+    // one view per lane: the functions the view waves run per frame without the table (pose_inverse, rt_mul), and
+    // chain_entry at constant (a, b), which forms per lane what chain_entry_reg picks by weights.  Up to 64 views are
+    // one wave's work; the other waves wait at the barrier (every wave forming the transforms and the chain entries
+    // going round the waves measured slower: prologue barrier 6.6 -> 7.0 us at configs[3], profiles/r16/)
+    for (int v = tid; v < G * N; v += nth) {
+      const int fi = v / N, cv2 = v - fi * N;
+      double fp[7];
+#pragma unroll
+      for (int q = 0; q < 7; ++q) fp[q] = fpl[8 * fi + q];
+      const double* Lc = cst[cv2];
+      double Ri[9], ti[3], R[12];
+      pose_inverse(fp, Ri, ti);
+      rt_mul(Lc, Lc + 9, Ri, ti, R, R + 9);  // T_cam_w = L_cam T_f^-1
+      double* rec = VTl + v * kVtStride;
+#pragma unroll
+      for (int q = 0; q < 12; ++q) rec[q] = R[q];
+#pragma unroll
+      for (int e = 0; e < 36; ++e) rec[12 + e] = chain_entry(R, R + 9, fp + 4, e / 6, e % 6);
+    }
+  }
   __syncthreads();
   if (wave == 0) KB_TSB(d, 1);
 
@@ -1682,19 +1717,33 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
         if (wave == 0 && it < 8) KB_TSB(d, 2 + 2 * it);
         double* vb = (it & 1) ? VB1 : VB;
         const int2 fvn = d.fview[(size_t)min(f + 1, f1 - 1) * N + cam];  // the next frame's view (first loads below)
-        double fp[7];
+        // T_cam_w = (R | t) and the chain G of the view: from the block's table (a wave-uniform record: all reads
+        // issued, then used), or computed here by every lane where the block has no table
+        double R[9], t[3], tm[3] = {0.0, 0.0, 0.0};
+        int go;  // the view's chain G (6 x 6, row-major) as an offset into sm
+        if constexpr (vt) {
+          const int ro = (int)(VTl - sm) + (it * N + cam) * kVtStride;
 #pragma unroll
-        for (int q = 0; q < 7; ++q) fp[q] = fpl[8 * it + q];
-        double Ri[9], ti[3], R[9], t[3];
-        pose_inverse(fp, Ri, ti);
-        rt_mul(Lc, Lc + 9, Ri, ti, R, t);  // T_cam_w = L_cam T_f^-1
-        // the view's chain G (6 x 6) for the expansion, formed while the first pass's MFMAs run: every lane holds
-        // T_cam_w and the frame translation in registers, so lane e < 36 picks entry e by selects (no LDS staging;
-        // wave 0's first v-row segment 2.2 -> 1.2 us, the frame period unchanged: the second view wave of each SIMD
-        // sets it)
-        double* Gm = Wv + cam * 36;
+          for (int q = 0; q < 9; ++q) R[q] = sm[ro + q];
+#pragma unroll
+          for (int q = 0; q < 3; ++q) t[q] = sm[ro + 9 + q];
+          go = ro + 12;
+        } else {
+          double fp[7];
+#pragma unroll
+          for (int q = 0; q < 7; ++q) fp[q] = fpl[8 * it + q];
+          double Ri[9], ti[3];
+          pose_inverse(fp, Ri, ti);
+          rt_mul(Lc, Lc + 9, Ri, ti, R, t);  // T_cam_w = L_cam T_f^-1
+#pragma unroll
+          for (int q = 0; q < 3; ++q) tm[q] = fp[4 + q];
+          go = (int)(Wv - sm) + cam * 36;
+        }
+        // without the table the chain is formed while the first pass's MFMAs run: every lane holds T_cam_w and the
+        // frame translation in registers, so lane e < 36 picks entry e by selects (no LDS staging; wave 0's first
+        // v-row segment 2.2 -> 1.2 us, the frame period unchanged: the second view wave of each SIMD sets it)
         auto make_g = [&]() {
-          if (lane < 36) Gm[lane] = chain_entry_reg(R, t, fp + 4, lane / 6, lane % 6);
+          if (!vt && lane < 36) sm[go + lane] = chain_entry_reg(R, t, tm, lane / 6, lane % 6);
         };
 #ifdef KB_SYRK16
         v4d acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
@@ -1709,6 +1758,15 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
         const int o0 = fv.x, o1 = fv.y;
         const bool stv = (wave == 0 || wave == N - 1) && it == 2;  // diagnostic stamps: one steady-state frame
         const int sto = wave == 0 ? 130 : 160;
+#ifdef KB_STAMPS
+        if (stv) {  // the transform in hand, not only its reads issued
+#pragma unroll
+          for (int q = 0; q < 9; ++q) KB_KEEP(R[q]);
+#pragma unroll
+          for (int q = 0; q < 3; ++q) KB_KEEP(t[q]);
+          KB_TSB(d, sto + 9);
+        }
+#endif
         int pass = 0;
         for (int base = o0; base < o1; base += 64, ++pass) {  // 64 corners per pass: the u rows, then the v rows
           const int k = base + lane;
@@ -2061,7 +2119,7 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
           const int k = k0 + 4 * st;
-          const double g = Gm[min(k, 5) * 6 + min(i16, 5)];
+          const double g = sm[go + min(k, 5) * 6 + min(i16, 5)];
           gb[st] = (k < 6 && i16 < 6) ? g : 0.0;
         }
         v4d dv = {0.0, 0.0, 0.0, 0.0};

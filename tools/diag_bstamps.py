@@ -33,6 +33,9 @@ for w, o in (("wave 0", 130), ("last view wave", 160)):
         names[o + 4 * ps + 2] = f"  [{w}] f2 pass {ps} u MFMAs done"
         names[o + 4 * ps + 3] = f"  [{w}] f2 pass {ps} v MFMAs done"
     names[o + 8] = f"  [{w}] f2 expansion done"
+    names[o + 9] = f"  [{w}] f2 transform ready"
+names[18] = "prologue: round-1 values in hand"
+names[19] = "prologue: frame steps done, poses staged"
 for w in range(4):
     names[176 + w] = f"    [fw{w}] f2 products done"
     names[184 + w] = f"    [fw{w}] f2 sums done"
