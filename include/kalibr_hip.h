@@ -484,6 +484,26 @@ int kb_sp_revert(kb_sp_handle* h);
  * (block (k, k+d)), gc [C], gs [6K], cost. */
 int kb_sp_get_system(kb_sp_handle* h, double* Hcc, double* Hsc, double* Hband, double* gc, double* gs,
                      double* cost);
+/* Optimizer::computeDiagonalCovariances / BlockCholeskyLinearSystemSolver::computeCovarianceBlocks
+ * (aslam_backend/src/Optimizer2.cpp:365-402, BlockCholeskyLinearSystemSolver.cpp:122-148) for the spline system, on the
+ * device: blocks of (H + lambda^2 I)^-1 of the last kb_sp_build under the conditioner in force, by the
+ * selected inverse over the factors the default solve leaves in HBM (no dense inverse is formed):
+ *   Ptt   [C][C]        Sigma_theta,theta (intrinsics, baselines, T_c0_b, IMU biases and gravity), exactly symmetric
+ *   Pst   [6K][C]       Sigma_s,theta, the coefficients' rows against theta (may be NULL)
+ *   Pband [K][4][6][6]  Sigma(c_k, c_k+d), d = 0..3, in kb_sp_get_system's Hband layout (zeros where k + d >= K; may be
+ *                       NULL); blocks between coefficients further apart are not produced
+ * *ok = 0 exactly when kb_sp_solve would report 0 (outputs untouched then).  A query: it runs kb_sp_solve's launches
+ * first, so dx, the solved flag and the scalars are exactly as a kb_sp_solve under the same conditioner leaves them, and
+ * the state is untouched.  It inverts the system kb_sp_build made: motion-error and prior terms are part of it, and so
+ * are M-estimator weights and corner invR of a weighted handle (the reference's useMEstimator = false covariance is the
+ * caller's to get, by clearing the estimators before the build).  Needs kb_sp_build.  Refused on a handle created under
+ * KSP_PARTITION=1, KSP_ZS=0 or KSP_DEEP=1: only the default solve keeps every node's factor.  A KSP_ZSF=0 handle
+ * returns the bits of a default one: the query sums the camera block's Schur complement in one fixed order itself.
+ * kb_sp_curve_covariance: the same pipeline, then P [n][6][6], the covariance of the curve value [p | rotation vector]
+ * at times[q] (linear in its four active coefficients, weights of derivative 0 as kb_sp_upload evaluates them); a time
+ * outside the spline interval is refused before any launch. */
+int kb_sp_covariance(kb_sp_handle* h, double* Ptt, double* Pst, double* Pband, int* ok);
+int kb_sp_curve_covariance(kb_sp_handle* h, int32_t n, const double* times, double* P, int* ok);
 /* Optimizer2::optimize over the spline system (LM policy 0 / GN policy 1), host-driven loop over the
  * device passes; trace as kb_get_trace. */
 int kb_sp_optimize(kb_sp_handle* h, const kb_optimizer_options* opts, kb_solution* out);
@@ -510,8 +530,8 @@ int kb_sp_assemble_stats(kb_sp_handle* h, int32_t n, double* ms, double* bytes);
  * (df = 3), so it is the caller's to compute.
  * A handle with any estimator != NONE or an invR set is "weighted": kb_sp_eval_cost, kb_sp_build, kb_sp_get_system,
  * kb_sp_get_rhs, kb_sp_solve, kb_sp_optimize (LM and GN), kb_sp_run_gn_iterations, kb_sp_kernel_stats and
- * kb_sp_assemble_stats work on it through the same calls.  There is no build without the estimator (the spline path
- * has no covariance consumer).  Every setter voids the built system and the captured GN pass; a refused call leaves the
+ * kb_sp_assemble_stats work on it through the same calls.  kb_sp_covariance inverts the weighted system as built: there is no
+ * build without the estimator, so a covariance without it needs the estimators cleared first.  Every setter voids the built system and the captured GN pass; a refused call leaves the
  * handle as it was; a handle whose settings are all cleared launches exactly the kernels of a fresh one.
  * kb_sp_set_mestimator: before or after kb_sp_upload; m == NULL or kind NONE clears the family's estimator.
  * kb_sp_set_corner_invR: as kb_set_corner_invR (n == 0 or NULL clears, 1 one matrix for every corner, n_corners one per

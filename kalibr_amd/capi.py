@@ -37,7 +37,7 @@ EXPORTS = [
     "kb_sp_set_state", "kb_sp_get_state", "kb_sp_eval_cost", "kb_sp_build", "kb_sp_set_constant_conditioner",
     "kb_sp_solve", "kb_sp_get_rhs", "kb_sp_apply_update", "kb_sp_revert", "kb_sp_get_system", "kb_sp_optimize",
     "kb_sp_get_trace", "kb_sp_run_gn_iterations", "kb_sp_kernel_stats", "kb_sp_assemble_stats", "kb_sp_set_motion_error",
-    "kb_sp_set_position_priors",
+    "kb_sp_set_position_priors", "kb_sp_covariance", "kb_sp_curve_covariance",
     # robust terms on the spline path (kb_sp_set_corner_invR is in EXPORTS_MIXED_CASE below)
     "kb_sp_set_mestimator", "kb_sp_get_mestimator_weights",
 ]
@@ -218,6 +218,8 @@ def lib():
         L.kb_sp_set_mestimator.argtypes = [C.c_void_p, C.c_int32, C.POINTER(MEstimator)]
         L.kb_sp_set_corner_invR.argtypes = [C.c_void_p, dp, C.c_int32]
         L.kb_sp_get_mestimator_weights.argtypes = [C.c_void_p, C.c_int32, dp, dp]
+        L.kb_sp_covariance.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_int)]
+        L.kb_sp_curve_covariance.argtypes = [C.c_void_p, C.c_int32, dp, dp, C.POINTER(C.c_int)]
         _lib = L
     return _lib
 
@@ -717,6 +719,33 @@ class SplineSolver:
                                       _d(out["gs"]), C.byref(cost)))
         out["cost"] = cost.value
         return out
+
+    def covariance(self, cross=False, band=True, out=None):
+        """(ok, dict(Ptt [C][C], Pst [6K][C] or None, Pband [K][4][6][6] or None)): blocks of (H + lambda^2 I)^-1 of the
+        last build under the conditioner in force (kb_sp_covariance).  cross: also Sigma_s,theta; band: the coefficient
+        band in system()'s Hband layout.  out: a dict of arrays to fill (reused across calls); they keep their contents
+        when ok is False."""
+        Cc, K = self.C, self.K
+        out = {} if out is None else out
+        if out.get("Ptt") is None:
+            out["Ptt"] = np.zeros((Cc, Cc))
+        if cross and out.get("Pst") is None:
+            out["Pst"] = np.zeros((6 * K, Cc))
+        if band and out.get("Pband") is None:
+            out["Pband"] = np.zeros((K, 4, 6, 6))
+        ok = C.c_int(0)
+        _check(lib().kb_sp_covariance(self.h, _d(out["Ptt"]), _d(out["Pst"]) if cross else None,
+                                      _d(out["Pband"]) if band else None, C.byref(ok)))
+        return bool(ok.value), dict(Ptt=out["Ptt"], Pst=out["Pst"] if cross else None,
+                                    Pband=out["Pband"] if band else None)
+
+    def curve_covariance(self, times):
+        """(ok, P [n][6][6]): covariance of the curve value [p | rotation vector] at each time (kb_sp_curve_covariance)"""
+        t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        P = np.zeros((t.size, 6, 6))
+        ok = C.c_int(0)
+        _check(lib().kb_sp_curve_covariance(self.h, t.size, _d(t), _d(P), C.byref(ok)))
+        return bool(ok.value), P
 
     def optimize(self, policy="gn", lambda0=10.0, max_iterations=20, eps_x=1e-3, eps_j=1.0):
         o = OptimizerOptions(0 if policy == "lm" else 1, lambda0, max_iterations, eps_x, eps_j, 1, 0)

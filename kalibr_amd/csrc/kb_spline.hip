@@ -155,6 +155,19 @@ struct SpDev {
   double* irw;            // [2][M] per-sample ig sqrt(w_g) | ia sqrt(w_a) (imu_cc_wave<true> -> k_sp_assemble<true>)
   int q_term;             // k_sp_weights only: the family (kb_sp_term) and its outputs
   double *q_w, *q_s;
+  // covariance query (kb_sp_covariance): blocks of (H + lam2 I)^-1 by the selected inverse over the
+  // factors of a zs solve; allocated by the first query
+  double* cvE;            // [n][18][54 + C] L_j^-T [Z_Uin | Z_U | Z_R[:, :C] | L_j^-1] = [M_l | M_r | M_theta | P_j]
+  double* cvD;            // [n][324] Sigma_jj
+  double *cvSl, *cvSr;    // [n][324] Sigma_j,j-s | Sigma_j,j+s, s the stride node j was eliminated at
+  double* cvSt;           // [n][18][C] Sigma_j,theta
+  double* cvTT;           // [C][C] Sigma_theta,theta
+  double* cvPst;          // [6K][C]
+  double* cvPband;        // [K][4][6][6], kb_sp_get_system's Hband layout
+  int cvnq;               // k_sp_cov_curve: query times, their first coefficient, value weights and outputs
+  const int* cvk0;        // [cvnq]
+  const double* cvw;      // [cvnq][4]
+  double* cvP6;           // [cvnq][6][6]
 };
 
 using kb::rb_weight;
@@ -3019,6 +3032,298 @@ __global__ void k_sp_set_lam(SpDev d, double lam2) {
   }
 }
 
+// ---------------------------------------------------------------- covariance query
+// Blocks of (H + lam2 I)^-1 from the factors a zs solve leaves in HBM, by the selected inverse (Takahashi) over the
+// device's elimination order: odd multiples of s = 1, 2, 4, .., node 0, theta.  With N = (l = j - s, r = j + s, theta)
+// the neighbours of node j at its elimination, P_j = L_j^-T L_j^-1 and E_j = L_j^-T [Z_Uin | Z_U | Z_R[:, :C]]:
+//   Sigma_tt = S^-1,  Sigma_j,N = -E_j Sigma_NN,  Sigma_jj = P_j + E_j Sigma_NN E_j^T
+// walked from the top node down the strides (launch_bvec's order); Sigma_NN's blocks are all final by then.
+
+// Sigma_tt: k_sp_camsolve's register LDL^T of S (the same pivots, so the same ok), the unit factor through LDS, then one
+// column of the identity per lane in LDS; written from one triangle to both
+template <int CM>
+__global__ void __launch_bounds__(64) k_sp_cov_cam(SpDev d) {
+  constexpr int CP = CM + 1;
+  __shared__ double Lm[CM * CP];  // unit lower factor below the diagonal; the inverse on and above it
+  __shared__ double rDs[CM];
+  const int lane = threadIdx.x, C = d.C;
+  const int li = lane < C ? lane : 0;
+  {
+    double a[CM];
+#pragma unroll
+    for (int c = 0; c < CM; ++c) a[c] = d.Sf[li * C + (c < C ? c : 0)];
+#pragma unroll
+    for (int c = 0; c < CM; ++c) a[c] = (lane < C && c < C) ? a[c] : (lane == c ? 1.0 : 0.0);
+    bool ok = true;
+    double rD = 1.0;
+#pragma unroll
+    for (int k = 0; k < CM; ++k) {
+      const double Dk = rdlane(a[k], k);
+      ok = ok && (Dk > 0.0);
+      const double rdk = ksp_recip1(Dk);
+      rD = (lane == k) ? rdk : rD;
+      const double f = (lane > k) ? a[k] * rdk : 0.0;
+#pragma unroll
+      for (int j = k + 1; j < CM; ++j) a[j] -= f * rdlane(a[j], k);
+    }
+    if (lane == 0 && !ok) d.sc[SC_OK] = 0.0;
+    // lane i holds Ltilde[i][k] D_k (k < i): the unit factor's row i
+#pragma unroll
+    for (int k = 0; k < CM; ++k) {
+      const double v = a[k] * rdlane(rD, k);
+      if (lane < CM) Lm[lane * CP + k] = v;
+    }
+    if (lane < CM) rDs[lane] = rD;
+  }
+  __syncthreads();
+  // lane e solves column e of the identity on rows i >= e only (L^-1 is lower triangular and the inverse symmetric, so
+  // rows >= e are self-contained in both sweeps); x_i lives at Lm[e][i], the factor's unused upper triangle, and the
+  // factor's entries are wave-uniform reads.  Sums over k in ascending (forward) and descending (backward) order.
+  const int e = lane;
+  if (e < CM) {
+    double* xe = Lm + e * CP;
+    for (int i = 0; i < CM; ++i) {  // L y = e_e
+      double acc = i == e ? 1.0 : 0.0;
+#pragma unroll 8
+      for (int k = 0; k < i; ++k) {
+        const double yk = xe[k];
+        acc = fma(-Lm[i * CP + k], k >= e ? yk : 0.0, acc);
+      }
+      if (i >= e) xe[i] = acc;
+    }
+    for (int i = e; i < CM; ++i) xe[i] *= rDs[i];
+    for (int i = CM - 2; i >= 0; --i) {  // L^T x = D^-1 y
+      double acc = xe[i];
+#pragma unroll 8
+      for (int k = CM - 1; k > i; --k) acc = fma(-Lm[k * CP + i], xe[k], acc);
+      if (i >= e) xe[i] = acc;
+    }
+  }
+  __syncthreads();
+  for (int q = lane; q < C * C; q += 64) {
+    const int a = q / C, b = q - a * C;
+    d.cvTT[q] = Lm[min(a, b) * CP + max(a, b)];
+  }
+}
+
+// every node at once: [M_l | M_r | M_theta | P_j] = L_j^-T [Z_Uin | Z_U | Z_R[:, :C] | L_j^-1] (18 x (54 + C), row-major
+// into cvE).  One wave per node, four per block, wave-local LDS: L | 1/diag | T [18][ts].  Node 0 has no spline
+// neighbour (k_sp_top / the top level write its Z_R only): its M_l, M_r are zeros.
+__global__ void __launch_bounds__(256) k_sp_cov_prep(SpDev d) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, m = d.m, wc = 36 + m, C = d.C;
+  const int w = 36 + C, ew = w + NB, ts = ew | 1;
+  const int j = 4 * blockIdx.x + wave;
+  if (j >= d.n) return;  // wave-uniform
+  double* L = sm + (size_t)wave * (NB * NB + NB + NB * ts);
+  double* id = L + NB * NB;
+  double* T = id + NB;
+  const double* Z = d.Z + (size_t)j * NB * wc;
+  {  // every load in flight before the LDS stores (k_sp_bprep's staging)
+    constexpr int UL = (NB * NB + 63) / 64, UT = (NB * (36 + MAXC) + 63) / 64;
+    double lv[UL], tv[UT];
+    const double* Lj = d.Lf + (size_t)j * NB * NB;
+    const int nt = NB * w;
+    const float rinv = 1.0f / (float)w;
+#pragma unroll
+    for (int u = 0; u < UL; ++u) lv[u] = Lj[min(lane + 64 * u, NB * NB - 1)];
+#pragma unroll
+    for (int u = 0; u < UT; ++u) {
+      const int q = min(lane + 64 * u, nt - 1), r = div_small(q, rinv);
+      tv[u] = Z[r * wc + q - w * r];
+    }
+    const double iv = d.Lid[(size_t)j * NB + min(lane, NB - 1)];
+#pragma unroll
+    for (int u = 0; u < UL; ++u)
+      if (lane + 64 * u < NB * NB) L[lane + 64 * u] = lv[u];
+#pragma unroll
+    for (int u = 0; u < UT; ++u) {
+      const int q = lane + 64 * u, r = div_small(q, rinv), c = q - w * r;
+      if (q < nt) T[r * ts + c] = (j == 0 && c < 36) ? 0.0 : tv[u];
+    }
+    if (lane < NB) id[lane] = iv;
+    for (int q = lane; q < NB * NB; q += 64) T[(q / NB) * ts + w + q % NB] = (q / NB == q % NB) ? 1.0 : 0.0;
+  }
+  KSP_WAVE_SYNC();
+  node_forward_lean(L, id, T + w, ts, NB, T + w, ts, lane, 64);  // L^-1, in place (a lane owns its column)
+  KSP_WAVE_SYNC();
+  node_backsolve_lean(L, id, T, ts, ew, d.cvE + (size_t)j * NB * ew, lane, 64);
+}
+
+// one stride of the walk: a block per node j = s + 2 s b (s = 0: the top node, N = (theta)).  Sigma_NN (w x w,
+// w = 36 + C, order [l | r | theta]) is gathered into LDS -- Sigma_ll, Sigma_rr, Sigma_l,theta, Sigma_r,theta from the
+// nodes' own blocks, Sigma_lr from whichever of l, r is the odd multiple of 2 s (its Sigma_jr, or its Sigma_jl
+// transposed), Sigma_tt -- then G = E_j Sigma_NN and E_j Sigma_NN E_j^T = G E_j^T on v_mfma_f64_16x16x4f64 tiles (the
+// fragment layout of level_products): 18 rows in two row tiles (18 of 32 rows carry data), k in steps of 4 in a fixed
+// order.  Rows and columns outside a part are clamped to valid LDS and their outputs not stored; k >= w is masked in A.
+__global__ void __launch_bounds__(256) k_sp_cov_level(SpDev d, int s) {
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const int tid = threadIdx.x, nth = blockDim.x, C = d.C, w = 36 + C, ew = w + NB, ss = w + 1;
+  const int j = s + 2 * s * (int)blockIdx.x;
+  if (j >= d.n) return;  // block-uniform
+  const int l = j - s, r = j + s;
+  const bool hl = s > 0, hr = s > 0 && r < d.n;
+  const bool lodd = hl && ((l / (2 * s)) & 1);  // l was eliminated at stride 2 s (its right neighbour is r)
+  double* Sg = sm;                  // [w][ss]
+  double* E = Sg + (size_t)w * ss;  // [18][ss]
+  double* G = E + NB * ss;          // [18][ss]
+  double* Pj = G + NB * ss;         // [18][19] P_j, then Sigma_jj
+  const double* Dl = d.cvD + (size_t)(hl ? l : j) * NB * NB;
+  const double* Dr = d.cvD + (size_t)(hr ? r : j) * NB * NB;
+  const double* Tl = d.cvSt + (size_t)(hl ? l : j) * NB * C;
+  const double* Tr = d.cvSt + (size_t)(hr ? r : j) * NB * C;
+  const double* Xlr = lodd ? d.cvSr + (size_t)l * NB * NB : d.cvSl + (size_t)(hr ? r : j) * NB * NB;
+  const double* Ej = d.cvE + (size_t)j * NB * ew;
+  const double* TT = d.cvTT;  // (the lambdas below capture locals only: a captured `d` is copied to scratch)
+  const float rw = 1.0f / (float)w, rew = 1.0f / (float)ew;
+  // Sigma_NN: entry (a, b) from its block's upper half (a's part <= b's part); an absent neighbour's blocks are zeros
+  // (the load goes to a valid address all the same).  Eight loads in flight per thread (ksp_batched's pattern, spelt
+  // out: as lambdas these bodies were not inlined and their captures went through scratch).
+  for (int q0 = tid; q0 < w * w; q0 += 8 * nth) {
+    double v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int q = min(q0 + u * nth, w * w - 1);
+      int a = div_small(q, rw), b = q - a * w;
+      const int lo = min(a, b);
+      b = max(a, b);
+      a = lo;
+      const int pa = a < NB ? 0 : a < 2 * NB ? 1 : 2, pb = b < NB ? 0 : b < 2 * NB ? 1 : 2;
+      const int ia = a - (pa == 2 ? 36 : NB * pa), ib = b - (pb == 2 ? 36 : NB * pb);
+      const double* p;
+      bool on;
+      if (pb == 2) {
+        p = (pa == 2 ? TT : pa == 0 ? Tl : Tr) + ia * C + ib;
+        on = pa == 2 || (pa == 0 ? hl : hr);
+      } else if (pa == pb) {
+        p = (pa == 0 ? Dl : Dr) + ia * NB + ib;
+        on = pa == 0 ? hl : hr;
+      } else {  // (l, r)
+        p = Xlr + (lodd ? ia * NB + ib : ib * NB + ia);
+        on = hl && hr;
+      }
+      const double x = *p;
+      v[u] = on ? x : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int q = q0 + u * nth, a = div_small(q, rw);
+      if (q < w * w) Sg[a * ss + q - a * w] = v[u];
+    }
+  }
+  for (int q0 = tid; q0 < NB * ew; q0 += 8 * nth) {
+    double v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = Ej[min(q0 + u * nth, NB * ew - 1)];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int q = q0 + u * nth, a = div_small(q, rew), c = q - a * ew;
+      if (q < NB * ew) {
+        if (c < w)
+          E[a * ss + c] = v[u];
+        else
+          Pj[a * (NB + 1) + c - w] = v[u];
+      }
+    }
+  }
+  __syncthreads();
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, nw = nth >> 6, i16 = lane & 15, kq = lane >> 4;
+  const int nct = (w + 15) >> 4;
+  for (int t = wave; t < 2 * nct; t += nw) {  // G = E Sigma_NN
+    const int ti = t / nct, tj = t - ti * nct;
+    const int ra = min(16 * ti + i16, NB - 1), c = 16 * tj + i16, cc = min(c, w - 1);
+    v4d_t acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 5
+    for (int k0 = 0; k0 < w; k0 += 4) {
+      const int k = k0 + kq, kc = min(k, w - 1);
+      const double a = k < w ? E[ra * ss + kc] : 0.0;
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Sg[kc * ss + cc], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int row = 16 * ti + kq + 4 * rr;
+      if (row < NB && c < w) G[row * ss + c] = acc[rr];
+    }
+  }
+  __syncthreads();
+  // Sigma_j,N = -G: [Sigma_jl | Sigma_jr | Sigma_j,theta]
+  for (int q = tid; q < NB * w; q += nth) {
+    const int a = div_small(q, rw), c = q - a * w;
+    const double v = -G[a * ss + c];
+    if (c < NB)
+      d.cvSl[(size_t)j * NB * NB + a * NB + c] = v;
+    else if (c < 2 * NB)
+      d.cvSr[(size_t)j * NB * NB + a * NB + c - NB] = v;
+    else
+      d.cvSt[(size_t)j * NB * C + a * C + c - 2 * NB] = v;
+  }
+  for (int t = wave; t < 4; t += nw) {  // Sigma_jj = P_j + G E^T
+    const int ti = t >> 1, tj = t & 1;
+    const int ra = min(16 * ti + i16, NB - 1), c = 16 * tj + i16, cc = min(c, NB - 1);
+    v4d_t acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 5
+    for (int k0 = 0; k0 < w; k0 += 4) {
+      const int k = k0 + kq, kc = min(k, w - 1);
+      const double a = k < w ? G[ra * ss + kc] : 0.0;
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, E[cc * ss + kc], acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int row = 16 * ti + kq + 4 * rr;
+      if (row < NB && c < NB) Pj[row * (NB + 1) + c] += acc[rr];
+    }
+  }
+  __syncthreads();
+  for (int q = tid; q < NB * NB; q += nth) {  // from the upper triangle to both
+    const int a = q / NB, b = q % NB;
+    d.cvD[(size_t)j * NB * NB + q] = Pj[min(a, b) * (NB + 1) + max(a, b)];
+  }
+}
+
+// the outputs in the layouts of kb_sp_get_system: block k of the grid fills Pband[k][0..3] (coefficient pairs (k, k + dd);
+// zeros where k + dd >= K) and rows 6 k .. 6 k + 5 of Pst.  A pair in one node reads Sigma_jj; a pair across nodes i, i + 1
+// reads the odd one's cross block (stride 1): Sigma_i,r, or Sigma_i+1,l transposed.  The padded slots of the last node
+// are never indexed.
+__global__ void __launch_bounds__(256) k_sp_cov_gather(SpDev d) {
+  const int k = blockIdx.x, tid = threadIdx.x, C = d.C;
+  const int i = k / SB, rk = 6 * (k % SB);
+  for (int q = tid; q < ORD * 36; q += blockDim.x) {
+    const int dd = q / 36, a = (q % 36) / 6, b = q % 6, k2 = k + dd;
+    double v = 0.0;
+    if (k2 < d.K) {
+      const int i2 = k2 / SB, rk2 = 6 * (k2 % SB);
+      if (i2 == i)
+        v = d.cvD[(size_t)i * NB * NB + (rk + a) * NB + rk2 + b];
+      else if (i & 1)
+        v = d.cvSr[(size_t)i * NB * NB + (rk + a) * NB + rk2 + b];
+      else
+        v = d.cvSl[(size_t)i2 * NB * NB + (rk2 + b) * NB + rk + a];
+    }
+    d.cvPband[(size_t)k * ORD * 36 + q] = v;
+  }
+  for (int q = tid; q < 6 * C; q += blockDim.x)
+    d.cvPst[(size_t)6 * k * C + q] = d.cvSt[(size_t)i * NB * C + rk * C + q];
+}
+
+// covariance of the curve value [p | theta](t) = sum_a w_a c_{k0+a}: sum_{a,b} w_a w_b Sigma(c_{k0+a}, c_{k0+b}) from
+// Pband, one wave per query time (lane = entry of the 6 x 6), the 16 terms in a fixed order
+__global__ void __launch_bounds__(64) k_sp_cov_curve(SpDev d) {
+  const int t = blockIdx.x, lane = threadIdx.x;
+  if (t >= d.cvnq || lane >= 36) return;
+  const int k0 = d.cvk0[t], r = lane / 6, c = lane % 6;
+  const double* w = d.cvw + 4 * (size_t)t;
+  double acc = 0.0;
+#pragma unroll
+  for (int a = 0; a < ORD; ++a)
+#pragma unroll
+    for (int b = 0; b < ORD; ++b) {
+      const double v = b >= a ? d.cvPband[((size_t)(k0 + a) * ORD + (b - a)) * 36 + r * 6 + c]
+                              : d.cvPband[((size_t)(k0 + b) * ORD + (a - b)) * 36 + c * 6 + r];
+      acc = fma(w[a] * w[b], v, acc);
+    }
+  d.cvP6[(size_t)t * 36 + lane] = acc;
+}
+
 }  // namespace ksp
 
 // ==================================================================================================
@@ -3177,6 +3482,10 @@ struct kb_sp_handle {
   size_t lds_deep = 0;
   std::vector<double> trace;
   double* host_sc = nullptr;  // pinned scalars
+  // covariance query: buffers and launch sizes made by the first kb_sp_covariance / kb_sp_curve_covariance
+  bool cov_ready = false;
+  const void* fn_covcam = nullptr;
+  size_t lds_cprep = 0, lds_clevel = 0;
 
   template <class T>
   int alloc(T** p, size_t cnt) {
@@ -4181,6 +4490,135 @@ int kb_sp_get_system(kb_sp_handle* h, double* Hcc, double* Hsc, double* Hband, d
     }
   }
   return 0;
+}
+
+}  // extern "C"
+
+namespace {
+// the checks of a covariance query and, on the first one, its buffers and launch sizes
+int cov_prepare(kb_sp_handle* h, const char* who) {
+  if (!h->built) return fail(std::string(who) + ": build first");
+  SpDev& d = h->d;
+  if (!d.zs) {
+    // the factors the recursion reads (Lf, Lid and Z of every node, the top node's included) are complete only after
+    // the default solve
+    const char* why = !h->use_cr       ? "KSP_PARTITION=1 (the partitioned band solve keeps per-chunk factors)"
+                      : h->s_deep != 0 ? "KSP_DEEP=1 (the deep levels' factors stay in the one block's LDS)"
+                                       : "KSP_ZS=0 (the C + 1 column back substitution does not keep the top node's Z)";
+    return fail(std::string(who) + ": no covariance on a handle created under " + why);
+  }
+  if (h->cov_ready) return 0;
+  const int C = h->C, w = 36 + C, ew = w + NB;
+  h->lds_cprep = sizeof(double) * 4 * (NB * NB + NB + NB * (size_t)(ew | 1));
+  h->lds_clevel = sizeof(double) * ((size_t)w * (w + 1) + 2 * NB * (size_t)(w + 1) + NB * (NB + 1));
+  if (h->lds_cprep > 160 * 1024 || h->lds_clevel > 160 * 1024) return fail(std::string(who) + ": LDS budget exceeded");
+  const size_t n = (size_t)h->n;
+  if (h->alloc(&d.cvE, n * NB * ew) || h->alloc(&d.cvD, n * NB * NB) || h->alloc(&d.cvSl, n * NB * NB) ||
+      h->alloc(&d.cvSr, n * NB * NB) || h->alloc(&d.cvSt, n * NB * C) || h->alloc(&d.cvTT, (size_t)C * C) ||
+      h->alloc(&d.cvPst, (size_t)6 * h->K * C) || h->alloc(&d.cvPband, (size_t)h->K * ORD * 36))
+    return -1;
+  h->fn_covcam = C <= 16   ? (const void*)k_sp_cov_cam<16>
+                 : C <= 32 ? (const void*)k_sp_cov_cam<32>
+                 : C <= 40 ? (const void*)k_sp_cov_cam<40>
+                 : C <= 48 ? (const void*)k_sp_cov_cam<48>
+                           : (const void*)k_sp_cov_cam<64>;
+  // (the attribute belongs to the kernel, not to the handle: the widest rig's size, so that handles of different C
+  // do not lower each other's limit)
+  constexpr int wm = 36 + MAXC, em = wm + NB;
+  KSP_HIP(hipFuncSetAttribute((const void*)k_sp_cov_prep, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(sizeof(double) * 4 * (NB * NB + NB + NB * (em | 1)))));
+  KSP_HIP(hipFuncSetAttribute((const void*)k_sp_cov_level, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(sizeof(double) * (wm * (wm + 1) + 2 * NB * (wm + 1) + NB * (NB + 1)))));
+  h->cov_ready = true;  // (a captured pass holds an older SpDev by value: the fields above are read by the query only)
+  return 0;
+}
+
+// kb_sp_solve's launches, then (zsf) S summed again in a fixed order, then the selected inverse (3 + log2 launches + the
+// gather; with `curve` the curve kernel), one stream sync; *ok and h->solved as kb_sp_solve leaves them (k_sp_cov_cam
+// clears ok as well should the re-summed S, which differs from the solve's by rounding, have a non-positive pivot)
+int cov_pipeline(kb_sp_handle* h, bool curve, int* ok) {
+  SpDev& d = h->d;
+  void* args[] = {&d};
+  hipLaunchKernelGGL(k_sp_set_lam, dim3(1), dim3(64), 0, h->stream, d, h->lambda * h->lambda);
+  if (launch_solve(h)) return -1;
+  hipLaunchKernelGGL(k_sp_update, dim3(d.n), dim3(64), 0, h->stream, d, 0);
+  if (d.zsf) {
+    // S summed once more in k_sp_zschur's order (every node's Z_R^T Z_R in its block of four, node 0 first), into
+    // d.Sf: with zsf the solve added node 0's term last (k_sp_schur_red), so its S differs from a KSP_ZSF=0 handle's
+    // in the last bits, and Sigma would with it.  The solve is done with d.Sf by now (dx is written); the next solve
+    // forms it again.  The query's result then does not depend on how the solve's launches were arranged.
+    SpDev dc = d;
+    dc.zsf = 0;
+    hipLaunchKernelGGL(k_sp_zschur, dim3(d.nblk_s), dim3(256), h->lds_schur, h->stream, dc);
+    hipLaunchKernelGGL(k_sp_schur_red, dim3((d.Ws + 63) / 64), dim3(64 * RW), 0, h->stream, dc);
+  }
+  hipLaunchKernelGGL(k_sp_cov_prep, dim3((d.n + 3) / 4), dim3(256), h->lds_cprep, h->stream, d);
+  KSP_HIP(hipLaunchKernel(h->fn_covcam, dim3(1), dim3(64), args, 0, h->stream));
+  hipLaunchKernelGGL(k_sp_cov_level, dim3(1), dim3(256), h->lds_clevel, h->stream, d, 0);
+  for (int s = h->s_top / 2; s >= 1; s /= 2) {
+    const int cnt = d.n > s ? (d.n - s + 2 * s - 1) / (2 * s) : 0;
+    if (cnt) hipLaunchKernelGGL(k_sp_cov_level, dim3(cnt), dim3(256), h->lds_clevel, h->stream, d, s);
+  }
+  hipLaunchKernelGGL(k_sp_cov_gather, dim3(d.K), dim3(256), 0, h->stream, d);
+  if (curve) hipLaunchKernelGGL(k_sp_cov_curve, dim3(d.cvnq), dim3(64), 0, h->stream, d);
+  KSP_HIP(hipGetLastError());
+  if (read_scalars(h)) return -1;
+  *ok = h->host_sc[SC_OK] != 0.0;
+  h->solved = *ok != 0;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int kb_sp_covariance(kb_sp_handle* h, double* Ptt, double* Pst, double* Pband, int* ok) {
+  if (!h || !Ptt || !ok) return fail("kb_sp_covariance: null");
+  KSP_HIP(hipSetDevice(h->device));
+  if (cov_prepare(h, "kb_sp_covariance")) return -1;
+  if (cov_pipeline(h, false, ok)) return -1;
+  if (!*ok) return 0;  // the outputs stay untouched
+  const SpDev& d = h->d;
+  KSP_HIP(hipMemcpy(Ptt, d.cvTT, sizeof(double) * h->C * h->C, hipMemcpyDeviceToHost));
+  if (Pst) KSP_HIP(hipMemcpy(Pst, d.cvPst, sizeof(double) * 6 * h->K * h->C, hipMemcpyDeviceToHost));
+  if (Pband) KSP_HIP(hipMemcpy(Pband, d.cvPband, sizeof(double) * h->K * ORD * 36, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int kb_sp_curve_covariance(kb_sp_handle* h, int32_t n, const double* times, double* P, int* ok) {
+  if (!h || !times || !P || !ok) return fail("kb_sp_curve_covariance: null");
+  if (n < 1) return fail("kb_sp_curve_covariance: n must be positive");
+  KSP_HIP(hipSetDevice(h->device));
+  if (cov_prepare(h, "kb_sp_curve_covariance")) return -1;
+  std::vector<int> k0((size_t)n);
+  std::vector<double> w((size_t)n * 4);
+  for (int q = 0; q < n; ++q) {
+    k0[q] = basis_weights(h->knots, ORD, times[q], 0, w.data() + 4 * (size_t)q);
+    if (k0[q] < 0 || k0[q] + ORD > h->K) return fail("kb_sp_curve_covariance: time outside the spline interval");
+  }
+  SpDev& d = h->d;
+  int* dk = nullptr;
+  double *dw = nullptr, *dp = nullptr;
+  if (h->alloc(&dk, (size_t)n) || h->alloc(&dw, (size_t)n * 4) || h->alloc(&dp, (size_t)n * 36)) return -1;
+  int rc = 0;
+  if (hipMemcpyAsync(dk, k0.data(), sizeof(int) * n, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+      hipMemcpyAsync(dw, w.data(), sizeof(double) * 4 * n, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+    rc = fail("kb_sp_curve_covariance: upload failed");
+  d.cvnq = n;
+  d.cvk0 = dk;
+  d.cvw = dw;
+  d.cvP6 = dp;
+  if (!rc) rc = cov_pipeline(h, true, ok);
+  if (!rc && *ok && hipMemcpy(P, dp, sizeof(double) * 36 * n, hipMemcpyDeviceToHost) != hipSuccess)
+    rc = fail("kb_sp_curve_covariance: download failed");
+  hipStreamSynchronize(h->stream);
+  d.cvnq = 0;
+  d.cvk0 = nullptr;
+  d.cvw = nullptr;
+  d.cvP6 = nullptr;
+  h->release(dk);
+  h->release(dw);
+  h->release(dp);
+  return rc;
 }
 
 int kb_sp_optimize(kb_sp_handle* h, const kb_optimizer_options* o, kb_solution* out) {

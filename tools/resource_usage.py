@@ -1,6 +1,7 @@
 """Per-kernel register / scratch / occupancy summary of libkalibr_hip (hipcc -Rpass-analysis=kernel-resource-usage).
 
 usage: python tools/resource_usage.py [filter-substring] [extra hipcc flags...]
+A filter that contains "k_sp" reads kb_spline.hip instead of kb_capi.hip.
 """
 import re
 import subprocess
@@ -11,7 +12,8 @@ from kalibr_amd import build as B  # noqa: E402
 
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
 extra = sys.argv[2:]
-r = subprocess.run([B.HIPCC] + B.FLAGS + extra + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/tmp/ru.o", B.SRC],
+src = B.SRC_SPLINE if "k_sp" in flt else B.SRC  # the spline path's kernels are a translation unit of their own
+r = subprocess.run([B.HIPCC] + B.FLAGS + extra + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/tmp/ru.o", src],
                    capture_output=True, text=True)
 cur = None
 rows = {}
