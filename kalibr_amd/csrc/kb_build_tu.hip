@@ -47,9 +47,8 @@ const void* build_fn_w(int mb) {
 }
 
 // weighted handles in KB_ROBUST_BUILD_PIPE mode: k_buildp<.., WT = true>, the general and the fused GN pass.  The
-// diagnostic / timing variants of k_buildp carry no weights (null: kb_set_robust_build refuses the mode)
-#if defined(KB_CORNER_OLD) || defined(KB_SYRK16) || defined(KB_CORNER_CLAMP) || defined(KB_CORNER_NOZERO) || \
-    defined(KB_DIAG_NOPROJ) || defined(KB_DIAG_NOSYRK)
+// diagnostic timing variants of k_buildp carry no weights (null: kb_set_robust_build refuses the mode)
+#if defined(KB_DIAG_NOPROJ) || defined(KB_DIAG_NOSYRK)
 template <bool GN>
 const void* build_fn_pw(int, bool, bool) {
   return nullptr;

@@ -215,16 +215,7 @@ __device__ __forceinline__ double* cam_K(const KbDev& d, int slot) { return d.ca
 
 // 16x16 upper-packed helpers (row-major upper: a <= b)
 __host__ __device__ __forceinline__ int d16_index(int a, int b) { return a * 16 - a * (a - 1) / 2 + (b - a); }
-__device__ __forceinline__ void d16_rowcol(int e, int& a, int& b) {
-  int r = 0;
-  while (e >= 16 - r) {
-    e -= 16 - r;
-    ++r;
-  }
-  a = r;
-  b = r + e;
-}
-// closed form of d16_rowcol: row a = largest with a(33 - a)/2 <= e
+// row and column of packed index e in closed form: row a = largest with a(33 - a)/2 <= e
 __device__ __forceinline__ void d16_rowcol_fast(int e, int& a, int& b) {
   int r = (int)((33.0f - sqrtf(1089.0f - 8.0f * (float)e)) * 0.5f);
   r = r < 0 ? 0 : (r > 15 ? 15 : r);

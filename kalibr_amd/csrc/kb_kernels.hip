@@ -105,29 +105,6 @@ __device__ __forceinline__ double rot_d(double v) {
   return __longlong_as_double(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
 
-// lane k's value to every lane of its 16-lane row (DPP row_newbcast, gfx90a+): a plain VALU move, without the
-// v_readlane -> SGPR -> VALU round trip.  k must fold to a constant (unrolled loops).
-__device__ __forceinline__ double bcast16(double v, int k) {
-  switch (k) {
-    case 0: return dpp_d<0x150>(v);
-    case 1: return dpp_d<0x151>(v);
-    case 2: return dpp_d<0x152>(v);
-    case 3: return dpp_d<0x153>(v);
-    case 4: return dpp_d<0x154>(v);
-    case 5: return dpp_d<0x155>(v);
-    case 6: return dpp_d<0x156>(v);
-    case 7: return dpp_d<0x157>(v);
-    case 8: return dpp_d<0x158>(v);
-    case 9: return dpp_d<0x159>(v);
-    case 10: return dpp_d<0x15A>(v);
-    case 11: return dpp_d<0x15B>(v);
-    case 12: return dpp_d<0x15C>(v);
-    case 13: return dpp_d<0x15D>(v);
-    case 14: return dpp_d<0x15E>(v);
-    default: return dpp_d<0x15F>(v);
-  }
-}
-
 // wave-wide sum / max, fixed order, result uniform: row butterflies by rotation, then the 4 row values
 __device__ __forceinline__ double wave_sum_d(double v) {
   v += dpp_d<0x128>(v);
@@ -624,54 +601,6 @@ __device__ __forceinline__ int cidx_col(int e, int C) {
   return j;
 }
 
-// pair index of the chain K_{i,j} (j < i) in the pair-packed LDS arrays of k_buildp
-__device__ __forceinline__ int pidx(int i, int j) { return i * (i - 1) / 2 + j; }
-
-// entry (p, q) of H_cc (any order) or, q < 0, entry p of g_c, expanded from one block's per-camera sums:
-//   H_{I_i,I_i} = Hs_i[II]; H_{I_i,B_j} = Hs_i[Id] K_{i,j} (j < i); H_{B_j,B_k} = sum_{i > max(j,k)} K_{i,j}^T T_{i,k};
-//   g_{I_i} = Hs_i[I,15]; g_{B_j} = sum_{i > j} K_{i,j}^T Hs_i[d,15]
-// Hs [N][16][16] (rows 0..5 pose, 6..14 intrinsics, 15 the -e column), Kp / Tp [pair][6][6] with T_{i,k} = Hs_i[dd] K_{i,k}
-// (the same algebra as cam_entry_l / cam_grad_l over the finished sums; CalibrationTools.hpp:32-45 chain order)
-__device__ __forceinline__ double cam_expand_entry(int N, const int* ci, const double* Hs, const double* Tp,
-                                                   const double* Kp, int p, int q) {
-  const int kp = ci[p] >> 16, ip = (ci[p] >> 8) & 0xff, xp = ci[p] & 0xff;
-  double s = 0.0;
-  if (q < 0) {
-    if (kp == 0) return Hs[ip * 256 + (6 + xp) * 16 + 15];
-    for (int i = ip + 1; i < N; ++i) {
-      const double* K = Kp + pidx(i, ip) * 36;
-#pragma unroll
-      for (int a = 0; a < 6; ++a) s += K[a * 6 + xp] * Hs[i * 256 + a * 16 + 15];
-    }
-    return s;
-  }
-  const int kq = ci[q] >> 16, iq = (ci[q] >> 8) & 0xff, xq = ci[q] & 0xff;
-  if (kp == 0 && kq == 0) {
-    if (ip == iq) s = Hs[ip * 256 + (6 + xp) * 16 + 6 + xq];
-  } else if (kp == 0 && kq == 1) {
-    if (iq < ip) {
-      const double* K = Kp + pidx(ip, iq) * 36;
-#pragma unroll
-      for (int b = 0; b < 6; ++b) s += Hs[ip * 256 + (6 + xp) * 16 + b] * K[b * 6 + xq];
-    }
-  } else if (kp == 1 && kq == 0) {
-    if (ip < iq) {
-      const double* K = Kp + pidx(iq, ip) * 36;
-#pragma unroll
-      for (int a = 0; a < 6; ++a) s += K[a * 6 + xp] * Hs[iq * 256 + a * 16 + 6 + xq];
-    }
-  } else {
-    const int m = ip > iq ? ip : iq;
-    for (int i = m + 1; i < N; ++i) {
-      const double* K = Kp + pidx(i, ip) * 36;
-      const double* T = Tp + pidx(i, iq) * 36;
-#pragma unroll
-      for (int a = 0; a < 6; ++a) s += K[a * 6 + xp] * T[a * 6 + xq];
-    }
-  }
-  return s;
-}
-
 // Gauss-Jordan elimination of [H_ff + lam2 I | H_fc | g_f] by one wave, lanes = columns (slot s: column
 // lane + 64 s), rows 0..5 in registers; pivot column k broadcast with v_readlane.  No pivoting: H_ff is SPD,
 // the pivots are the squared Cholesky diagonal (all > 0 iff positive definite).  Ends with [I | A | b]:
@@ -728,76 +657,9 @@ __device__ __forceinline__ bool frame_gj(const KbDev& d, int f, const double* Hf
 
 // [A | b] = (H_ff + lam2 I)^-1 [H_fc | g_f] by LDL^T of the 6 x 6 block, factored redundantly in every lane's
 // registers (no cross-lane broadcast: a short dependent chain, which matters when the wave shares its SIMD with
-// MFMA-heavy waves), then each lane solves its columns lane and lane + 64 of [H_fc | g_f] (P, rows of 6).
-// Writes Q (rows of 6, columns 0..C) and, if `store`, A_f / b_f to HBM.  Returns false if not positive definite.
-__device__ __forceinline__ bool frame_ldl(const KbDev& d, int f, const double* Hff, double lam2, const double* P,
-                                          double* Q, int CZ, int lane, bool store, bool stamp = false) {
-  const int C = d.C;
-  double L[6][6], Di[6];
-  if (stamp) KB_TSB(d, 140);
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-#pragma unroll
-    for (int j = 0; j <= i; ++j) L[i][j] = Hff[i * 6 + j] + (i == j ? lam2 : 0.0);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    double v[6];
-#pragma unroll
-    for (int j = 0; j < k; ++j) v[j] = L[k][j] * L[j][j];  // L_kj D_j (D_j kept on the diagonal)
-    double dk = L[k][k];
-#pragma unroll
-    for (int j = 0; j < k; ++j) dk -= L[k][j] * v[j];
-    ok = ok && (dk > 0.0);
-    L[k][k] = dk;
-    Di[k] = recip_d(dk);
-#pragma unroll
-    for (int i = k + 1; i < 6; ++i) {
-      double s = L[i][k];
-#pragma unroll
-      for (int j = 0; j < k; ++j) s -= L[i][j] * v[j];
-      L[i][k] = s * Di[k];
-    }
-  }
-  if (stamp) KB_TSB(d, 141);
-#pragma unroll
-  for (int sl = 0; sl < 2; ++sl) {
-    const int c = lane + 64 * sl, cc = min(c, C);
-    double x[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {  // L y = b
-      double s = P[i * CZ + cc];
-#pragma unroll
-      for (int j = 0; j < i; ++j) s -= L[i][j] * x[j];
-      x[i] = s;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) x[i] *= Di[i];
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {  // L^T x = D^-1 y
-      double s = x[i];
-#pragma unroll
-      for (int j = i + 1; j < 6; ++j) s -= L[j][i] * x[j];
-      x[i] = s;
-    }
-    if (c <= C) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        Q[i * CZ + c] = x[i];
-        if (!store) continue;
-        if (c < C)
-          d.Af[((size_t)f * 6 + i) * C + c] = x[i];
-        else
-          d.bf[(size_t)f * 6 + i] = x[i];
-      }
-    }
-    if (stamp) KB_TSB(d, 142 + sl);
-  }
-  return ok;
-}
-
-// frame_ldl for a column range: each of the k_buildp frame waves factors the 6 x 6 block redundantly and solves its
-// own columns c0 <= c < c1 of [H_fc | g_f] into the shared Q (the frame waves meet before the Schur tiles read it)
+// MFMA-heavy waves), for a column range: each of the k_buildp frame waves solves its own columns c0 <= c < c1 of
+// [H_fc | g_f] (P, rows of CZ) into the shared Q (the frame waves meet before the Schur tiles read it) and into
+// A_f / b_f in HBM.  Returns false if not positive definite.
 __device__ __forceinline__ bool frame_ldl_cols(const KbDev& d, int f, const double* Hff, double lam2, const double* P,
                                                double* Q, int CZ, int lane, int c0, int c1, bool stamp = false) {
   const int C = d.C;
@@ -1406,37 +1268,22 @@ __device__ __forceinline__ void schur_tiles_accumulate6(const double* P, const d
 }
 
 // The register arrangement of k_buildp, per instantiation family.
-// KB_BUILDP_VGPR: the families whose MFMAs take VGPR accumulators (no AGPR use in the kernel, so the whole register
-//   budget is architectural and nothing is parked in AGPRs behind v_accvgpr_* copies): bit 0 the 12-wave one-model
-//   unweighted instantiations, bit 1 the 8-wave unweighted ones, bit 2 every other one (weighted; 12-wave multi-model).
-// KB_BUILDP_HOIST: what a view wave forms once per block instead of once per frame: bit 0 its lane id is opaque once
-//   per block in the 12-wave one-model unweighted instantiations (the compiler then keeps the lane-dependent
-//   addresses, masks and predicates of the SYRK and the expansion tail in registers; the weighted and the 12-wave
-//   multi-model view roles have no registers for them), bit 3 the same in the 8-wave two-model unweighted ones (the
-//   all-model one would go to scratch); bit 2, in the same families, the camera's first intrinsic column (ctab) is
-//   read from LDS once.  Bit 1: the frame waves' lane id once per block (measured, not kept).
-// The product: 3 and 13 (measured per family, profiles/r14/; 0 and 0 are the arrangement before round 14, which the
-// unmeasured families keep).
-#ifndef KB_BUILDP_VGPR
-#define KB_BUILDP_VGPR 3
-#endif
-#ifndef KB_BUILDP_HOIST
-#define KB_BUILDP_HOIST 13
-#endif
+// Measured per family (profiles/r14/); the families not measured (weighted; 12-wave multi-model) keep the arrangement
+// from before round 14.
+// VGPR accumulators for the MFMAs (no AGPR use in the kernel, so the whole register budget is architectural and nothing
+// is parked in AGPRs behind v_accvgpr_* copies): the unweighted 8-wave and 12-wave one-model instantiations.
 template <unsigned MM, int MW, bool WT>
 constexpr bool buildp_vgpr_acc() {
-  return ((KB_BUILDP_VGPR) >> (WT ? 2 : MW == 8 ? 1 : mm_nintr<MM>() != 0 ? 0 : 2)) & 1;
+  return !WT && (MW == 8 || mm_nintr<MM>() != 0);
 }
+// What a view wave forms once per block instead of once per frame: its lane id is opaque once per block (the compiler
+// then keeps the lane-dependent addresses, masks and predicates of the SYRK and the expansion tail in registers), and
+// the camera's first intrinsic column (ctab) is read from LDS once.  The unweighted 12-wave one-model and 8-wave
+// two-model instantiations: the weighted and the 12-wave multi-model view roles have no registers for it, and the
+// 8-wave all-model one would go to scratch.
 template <unsigned MM, int MW, bool WT>
-constexpr bool buildp_view_lane_once() {
-  if (WT) return false;
-  return MW == 8 ? (((KB_BUILDP_HOIST) >> 3) & 1) && __builtin_popcount(MM) <= 2
-                 : ((KB_BUILDP_HOIST) & 1) && mm_nintr<MM>() != 0;
-}
-template <unsigned MM, int MW, bool WT>
-constexpr bool buildp_view_cic_once() {
-  if (WT || !((KB_BUILDP_HOIST) & 4)) return false;
-  return MW == 8 ? __builtin_popcount(MM) <= 2 : mm_nintr<MM>() != 0;
+constexpr bool buildp_view_once() {
+  return !WT && (MW == 8 ? __builtin_popcount(MM) <= 2 : mm_nintr<MM>() != 0);
 }
 
 // MW: the most waves a block may have.  12 (8 cameras + 4 frame waves) caps the kernel at 168 VGPRs, so that two
@@ -1655,7 +1502,7 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
       if (tid + u * nth < nt3) tg[tid + u * nth] = tv[u];
     for (int q = tid + kTgU * nth; q < nt3; q += nth) tg[q] = d.target[q];
   }
-  const double* tgt = tg_lds ? tg : d.target;  // (KB_CORNER_OLD; the corner passes branch on tg_lds)
+  const double* tgt = tg_lds ? tg : d.target;
   (void)tgt;
   const double lam2 = lam * lam;
   if (tid == 0) {
@@ -1702,17 +1549,17 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
     const double* intr = cst[cam] + 12;
     v4d creg = {0.0, 0.0, 0.0, 0.0};  // the camera's local sums over the block's frames
     int lane_v = threadIdx.x & 63;
-    if constexpr (buildp_view_lane_once<MM, MW, WT>()) asm volatile("" : "+v"(lane_v));
+    if constexpr (buildp_view_once<MM, MW, WT>()) asm volatile("" : "+v"(lane_v));
     int cic = 0;  // the camera's first intrinsic column, read once where the family has it so (else per store)
-    if constexpr (buildp_view_cic_once<MM, MW, WT>()) cic = __builtin_amdgcn_readfirstlane(ctab[0][cam]);
+    if constexpr (buildp_view_once<MM, MW, WT>()) cic = __builtin_amdgcn_readfirstlane(ctab[0][cam]);
     for (int it = 0; it < G; ++it) {
       {
         // ---------------- phase B: view (f, cam)
         const int f = f0 + it;
-        // opaque per frame (see the frame waves), or once per block (buildp_view_lane_once): what depends on the
+        // opaque per frame (see the frame waves), or once per block (buildp_view_once): what depends on the
         // lane alone is then formed ahead of the frames
         int lane = lane_v;
-        if constexpr (!buildp_view_lane_once<MM, MW, WT>()) asm volatile("" : "+v"(lane));
+        if constexpr (!buildp_view_once<MM, MW, WT>()) asm volatile("" : "+v"(lane));
         const int mrow = lane >> 4, mcol = lane & 15;
         if (wave == 0 && it < 8) KB_TSB(d, 2 + 2 * it);
         double* vb = (it & 1) ? VB1 : VB;
@@ -1745,16 +1592,12 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
         auto make_g = [&]() {
           if (!vt && lane < 36) sm[go + lane] = chain_entry_reg(R, t, tm, lane / 6, lane % 6);
         };
-#ifdef KB_SYRK16
-        v4d acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-#else
         // the SYRK on v_mfma_f64_4x4x4f64 (4 blocks of 4 x 4): only the 10 upper 4 x 4 blocks of the symmetric 16 x 16
         // [J | e]^T [J | e] are formed (2.5 instructions of ~17 cycles per 4 rows, against one 64-cycle 16x16x4 that
         // also forms the 6 lower blocks).  accD: the diagonal blocks (b, b); accO1: (b, b+1 mod 4); accO2: (0,2), (1,3)
         // of two row quads.  Operand lane 16k + 4b + c supplies row k, column 4I_b + c (A) / 4J_b + c (B); block b's
         // entry (i, j) lands at lane 16i + 4b + j (tools/micro/mfma_f64_4x4_layout.hip).
         double accD = 0.0, accO1 = 0.0, accO2 = 0.0;
-#endif
         const int o0 = fv.x, o1 = fv.y;
         const bool stv = (wave == 0 || wave == N - 1) && it == 2;  // diagnostic stamps: one steady-state frame
         const int sto = wave == 0 ? 130 : 160;
@@ -1782,81 +1625,24 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
             if constexpr (WT)
               if (rb_pc) Ln = rb_load(d, kn);
           }
-#if defined(KB_CORNER_OLD) || defined(KB_SYRK16) || defined(KB_CORNER_CLAMP) || defined(KB_CORNER_NOZERO) || \
-    defined(KB_DIAG_NOPROJ) || defined(KB_DIAG_NOSYRK)
-          static_assert(!WT, "the diagnostic and timing variants of k_buildp carry no robust weights");
+#if defined(KB_DIAG_NOPROJ) || defined(KB_DIAG_NOSYRK)
+          static_assert(!WT, "the diagnostic timing variants of k_buildp carry no robust weights");
 #endif
-#ifdef KB_CORNER_OLD
-          double xu[16], xv[16];
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            xu[q] = 0.0;
-            xv[q] = 0.0;
-          }
-          if (k < o1) {  // one projection per corner: both Jacobian rows from the lane
-            const double X0 = tgt[3 * cid], X1 = tgt[3 * cid + 1], X2 = tgt[3 * cid + 2];
-            const double p0 = R[0] * X0 + R[1] * X1 + R[2] * X2 + t[0];
-            const double p1 = R[3] * X0 + R[4] * X1 + R[5] * X2 + t[1];
-            const double p2 = R[6] * X0 + R[7] * X1 + R[8] * X2 + t[2];
-            double u, w, Jp[6], Ji[2 * KB_MAX_INTR];
-            project_jac<MM>(model, intr, p0, p1, p2, u, w, Jp, Ji);
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-              double* xr = r ? xv : xu;
-              const double j0 = Jp[3 * r], j1 = Jp[3 * r + 1], j2 = Jp[3 * r + 2];
-              // J_delta = -Jp [I | [p]x]   (HomogeneousExpressionNode.cpp:71-81, boxMinus)
-              xr[0] = -j0;
-              xr[1] = -j1;
-              xr[2] = -j2;
-              xr[3] = -(j1 * p2 - j2 * p1);
-              xr[4] = -(-j0 * p2 + j2 * p0);
-              xr[5] = -(j0 * p1 - j1 * p0);
-              // intrinsics: -Jp, -Jd (CameraDesignVariable.hpp(impl):38-54)
-#pragma unroll
-              for (int q = 0; q < 9; ++q) xr[6 + q] = (q < nin) ? -Ji[KB_MAX_INTR * r + q] : 0.0;
-              xr[15] = -(r ? yv.y - w : yv.x - u);  // column 15 carries -e: H[:,15] = rhs part, H[15][15] = chi^2
-            }
-          }
-          const bool valid = true;
-#else
           // one projection per corner: both Jacobian rows from the lane.  The rows are written un-negated,
           // [dy/dtheta | e] = -[de/dtheta | -e]: the SYRK of a row and of its negation are bitwise equal, so the sign
           // flips of J_delta = -Jp [I | [p]x] and of the intrinsic rows -Jp, -Jd (CameraDesignVariable.hpp(impl):38-54)
-          // are not spent.  Lanes past the view's last corner leave xu / xv undefined and store zero rows instead (no
-          // 32-register zero initialisation per pass).
-          // (KB_CORNER_CLAMP: every lane projects a real corner -- lanes past the view's end hold the clamped last
-          // corner -- without the exec-mask branch and the zero initialisation, those lanes storing zero rows: more
-          // VGPRs spilled to AGPRs, k_buildp 93.1 -> 96.9 us; not the default)
+          // are not spent.  Lanes past the view's last corner keep zero rows (projecting a clamped corner on them
+          // instead, without the exec-mask branch and the zero initialisation, spilled more VGPRs to AGPRs: k_buildp
+          // 93.1 -> 96.9 us).
           const bool valid = k < o1;
           double xu[16], xv[16];
-#if !defined(KB_CORNER_NOZERO) && !defined(KB_CORNER_CLAMP)
 #pragma unroll
           for (int q = 0; q < 16; ++q) {
             xu[q] = 0.0;
             xv[q] = 0.0;
           }
-#endif
-#ifdef KB_CORNER_CLAMP
-          {
-#else
           if (valid) {
-#endif
-            double X0, X1, X2;
-#ifdef KB_CORNER_TGB
-            if (tg_lds) {  // the staged corners through ds_read (a select of the two pointers compiles to flat loads)
-              X0 = tg[3 * cid];
-              X1 = tg[3 * cid + 1];
-              X2 = tg[3 * cid + 2];
-            } else {
-              X0 = d.target[3 * cid];
-              X1 = d.target[3 * cid + 1];
-              X2 = d.target[3 * cid + 2];
-            }
-#else
-            X0 = tgt[3 * cid];
-            X1 = tgt[3 * cid + 1];
-            X2 = tgt[3 * cid + 2];
-#endif
+            const double X0 = tgt[3 * cid], X1 = tgt[3 * cid + 1], X2 = tgt[3 * cid + 2];
             const double p0 = R[0] * X0 + R[1] * X1 + R[2] * X2 + t[0];
             const double p1 = R[3] * X0 + R[4] * X1 + R[5] * X2 + t[1];
             const double p2 = R[6] * X0 + R[7] * X1 + R[8] * X2 + t[2];
@@ -1897,40 +1683,23 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
               }
             }
           }
-#endif
           if (stv && pass < 2) KB_TSB(d, sto + 4 * pass + 1);
-          // rows n .. 63 of a partial pass are zero: only the groups of 4 k-steps (16 rows) holding valid rows are
-          // issued (k-step ks = rows 4ks .. 4ks + 3, even ks into acc0, odd into acc1), the next group's operands in
-          // flight during the current group's MFMAs (one LDS round trip per group, not per MFMA).  Row = lane: the
-          // lanes of a write hit distinct LDS bank pairs at the 17-double row stride (KB_SYRK_DPP: by columns,
-          // kb_syrk_tile.h).
-#if defined(KB_SYRK_DPP) && !defined(KB_SYRK16)
+          // rows n .. 63 of a partial pass are zero: only the pairs of row quads (8 rows) holding valid rows are
+          // issued, the next pair's operands in flight during the current pair's MFMAs (one LDS round trip per pair,
+          // not per MFMA).  Row = lane: the lanes of a write hit distinct LDS bank pairs at the 17-double row stride
+          // (KB_SYRK_DPP: by columns, kb_syrk_tile.h).
+#ifdef KB_SYRK_DPP
 #define KB_TROW(q) kb_tile::store_idx(lane, q)  // by columns: conflict-free for the stores and for the two operand reads
 #else
 #define KB_TROW(q) (lane * XS + (q))
 #endif
-#ifdef KB_SYRK16
-          const int ng = (min(64, o1 - base) + 15) >> 4;
-#else
           const int np = (min(64, o1 - base) + 7) >> 3;  // pairs of row quads holding valid rows (the rest are zero)
-#endif
 #pragma unroll
           for (int r = 0; r < 2; ++r) {
-#if defined(KB_CORNER_NOZERO) || defined(KB_CORNER_CLAMP)
-            if (valid) {
-#pragma unroll
-              for (int q = 0; q < 16; ++q) Xw[KB_TROW(q)] = r ? xv[q] : xu[q];
-            } else {
-#pragma unroll
-              for (int q = 0; q < 16; ++q) Xw[KB_TROW(q)] = 0.0;
-            }
-#else
-            (void)valid;
 #pragma unroll
             for (int q = 0; q < 16; ++q) Xw[KB_TROW(q)] = r ? xv[q] : xu[q];
-#endif
             KB_WAVE_SYNC();
-#if defined(KB_SYRK_DPP) && !defined(KB_SYRK16)
+#ifdef KB_SYRK_DPP
             {
               // KB_SYRK_DPP (measured, not the default: DESIGN.md 3c, round 11): of the six operands per pair of row
               // quads (below) only the two diagonal ones q0, q1 are read from LDS, from the tile stored by columns
@@ -1972,7 +1741,7 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
                 mf(xr[pp & 1]);
               }
             }
-#elif !defined(KB_SYRK16)
+#else
             {
               // per pair of row quads (rows 8p .. 8p + 7): the diagonal-block operand of each quad (row mrow, column
               // mcol: the 16x16x4 operand), the (b, b+1) operand of each (column (mcol + 4) & 15), and the A / B
@@ -1981,7 +1750,9 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
               const int bq = (lane >> 2) & 3;
               const int oD = mrow * XS + mcol, oE = mrow * XS + ((mcol + 4) & 15);
               const int oA = bq < 2 ? oD : (4 + mrow) * XS + mcol - 8, oB = bq < 2 ? oD + 8 : (4 + mrow) * XS + mcol;
-              double xr[3][6];  // the operands of two pairs (the next pair's loads in flight during this pair's MFMAs)
+              // the operands of two pairs (the next pair's loads in flight during this pair's MFMAs).  Slot 2 is unused:
+              // declared [2][6] the kernel compiles to other instructions, and the measured code is kept
+              double xr[3][6];
               auto ld = [&](double* x, int pp) {
                 const double* xp = Xw + 8 * pp * XS;
                 x[0] = xp[oD];
@@ -2000,7 +1771,6 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
                 accO2 = __builtin_amdgcn_mfma_f64_4x4x4f64(x[4], x[5], accO2, 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
               };
-#ifndef KB_SYRK44_RING3  // (a ring of three pairs spills more to AGPRs and measured 0.4 % slower)
 #ifdef KB_DIAG_NOSYRK  // diagnostic timing variant only (wrong results): the SYRK MFMAs and their loads skipped
               (void)ld;
               (void)mf;
@@ -2019,43 +1789,6 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
                 mf(xr[pp & 1]);
               }
 #endif
-#else
-              ld(xr[0], 0);
-              if (np > 1) ld(xr[1], 1);
-#pragma unroll
-              for (int pp = 0; pp < 8; ++pp) {
-                if (pp >= np) break;  // wave-uniform
-                if (pp + 2 < np) ld(xr[(pp + 2) % 3], pp + 2);
-                mf(xr[pp % 3]);
-              }
-#endif
-            }
-#else
-            // groups g = 0..3 ping-pong between xa and xb: group g + 1's loads are issued before group g's MFMAs
-            double xa[4], xb[4];
-            auto ld = [&](double* x, int g) {
-#pragma unroll
-              for (int u = 0; u < 4; ++u) x[u] = Xw[(16 * g + 4 * u + mrow) * XS + mcol];
-              __builtin_amdgcn_sched_barrier(0);
-            };
-            auto mf = [&](const double* x) {
-              acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(x[0], x[0], acc0, 0, 0, 0);
-              acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x[1], x[1], acc1, 0, 0, 0);
-              acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(x[2], x[2], acc0, 0, 0, 0);
-              acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(x[3], x[3], acc1, 0, 0, 0);
-              __builtin_amdgcn_sched_barrier(0);
-            };
-            ld(xa, 0);
-            if (ng > 1) ld(xb, 1);
-            mf(xa);
-            if (ng > 1) {
-              if (ng > 2) ld(xa, 2);
-              mf(xb);
-              if (ng > 2) {
-                if (ng > 3) ld(xb, 3);
-                mf(xa);
-                if (ng > 3) mf(xb);
-              }
             }
 #endif
             if (stv && pass < 2) KB_TSB(d, sto + 4 * pass + 2 + r);
@@ -2076,13 +1809,6 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
         if (it == 3 && wave < 8) KB_TSB(d, 144 + wave);
         // f64 MFMA C/D layout: lane l, reg r -> row (l>>4) + 4r, col l&15
         v4d hv;
-#ifdef KB_SYRK16
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          hv[q] = acc0[q] + acc1[q];
-          creg[q] = creg[q] + hv[q];
-        }
-#else
         {
           // the upper blocks to the 16 x 16 C layout (hv[q] = H[mrow + 4q][mcol]) through the view's tile (free after
           // the SYRK): each block and its mirror written, the two quads' (0,2), (1,3) parts added first (lane + 8)
@@ -2105,7 +1831,6 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
             creg[q] = creg[q] + hv[q];
           }
         }
-#endif
         // expansion of view (f, cam) through the 6-D chain G on MFMA steps whose operands stay in registers:
         //   D = H[:, d] G  (A = the lane's own H registers: H is symmetric, so C-layout row r of a lane is A's k-step r;
         //   B = G from LDS), i.e. D[i][a] = P_v[a][i] with P_v = G^T H[d, :]: G^T H_dd, G^T H_dI, G^T g_d;
@@ -2155,7 +1880,7 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
           const int i = k0 + 4 * r;
           if (i16 < 6) {
             if (i >= 6 && i < 6 + nin) {
-              const int ci = buildp_view_cic_once<MM, MW, WT>() ? cic : ctab[0][cam];
+              const int ci = buildp_view_once<MM, MW, WT>() ? cic : ctab[0][cam];
               Pi[i16 * CZ + ci + i - 6] = dv[r];
               if (!gfu) d.Hfc[((size_t)f * 6 + i16) * C + ci + i - 6] = dv[r];
             } else if (i == 15) {
@@ -2304,10 +2029,7 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
     // the frame waves are the youngest waves of their SIMDs, so age-ordered issue serves them last; their frame sums
     // and elimination are on the per-frame critical path (priority 1: configs[3] 7,187 -> 7,232 GN it/s, the 250-frame
     // shard 14,568 -> 14,750; priority 3 measured the same)
-#ifndef KB_FW_PRIO
-#define KB_FW_PRIO 1
-#endif
-    __builtin_amdgcn_s_setprio(KB_FW_PRIO);
+    __builtin_amdgcn_s_setprio(1);
     v4d acc[TT];
     int tii[TT], tjj[TT];
 #pragma unroll
@@ -2320,10 +2042,6 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
     // spread over waves 0..1), then H_ff (its upper triangle, mirrored: 21 sums) and g_f on the cheapest wave: one
     // lane per output (243 at N = 7) over the 4 frame waves; the intrinsic columns are in place
     const int nbl = 36 * (N - 1), nsum = nbl + 27;
-#if (KB_BUILDP_HOIST) & 2
-    int lane_f = threadIdx.x & 63;
-    asm volatile("" : "+v"(lane_f));
-#endif
     for (int it = 0; it <= G; ++it) {
       if (it > 0) {
         // ---------------- phase A: sums of frame f = f0 + it - 1 over its views (camera order), the frame waves' share
@@ -2411,12 +2129,8 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
         const int f = f0 + it - 1;
         // an opaque lane id per frame: the lane-dependent addresses and selects of the elimination are recomputed
         // here instead of being hoisted out of the loop (which spills at this kernel's register budget)
-#if (KB_BUILDP_HOIST) & 2
-        const int lane = lane_f;
-#else
         int lane = threadIdx.x & 63;
         asm volatile("" : "+v"(lane));
-#endif
         if (fw == 0 && it <= 8) KB_TSB(d, 20 + 4 * (it - 1));
         double* P = (((it - 1) & 1) ? VB1 : VB) + N * 44;
 #ifdef KB_DIAG_NOFW
@@ -3702,13 +3416,13 @@ __device__ __forceinline__ int cidx(int i, int j, int C) { return j * (2 * C - j
 // i > q, holds W = L D (the unscaled sub-diagonal rows), a diagonal tile W strictly below its diagonal and D on it,
 // rD = 1 / D.  Row C then holds y = Ltilde^-1 b: the forward solve comes out of the factorisation, z = y D^-1.
 //
-// Panel q (columns 16q .. 16q+15) is factored by nF(q) <= 2 "factor" waves with one matrix row per lane:
-//   lanes 0..15 the rows of the diagonal tile (symmetric, read from the lower storage), lanes 16..63 the rows of three
-//   tiles below (factor wave fw: tiles q+1+3fw .. q+3+3fw).  Step k broadcasts the current row k (lane k) with
-//   v_readlane, so the diagonal factor and the panel's triangular solve are one 16-step register loop.
-// Before that, each factor wave applies panel q-1 to its own tiles on v_mfma_f64_16x16x4f64 (the lookahead column;
-// the diagonal tile into a private scratch copy), while 4 "update" waves apply panel q-1 to the remaining trailing
-// tiles (i, j), j > q.  One block barrier per panel; the 106-pivot chain runs on the factor waves only.
+// Panel q (columns 16q .. 16q+15) is factored by nF(q) <= 2 "factor" waves (panel_factor2): every 16-lane row of a
+//   wave holds the rows of the diagonal tile and the rows of one tile below (factor wave fw: tiles q+1+4fw .. q+4+4fw).
+//   Step k reads the current row k from lane k of the lane's own 16-lane row by DPP, so the diagonal factor and the
+//   panel's triangular solve are one 16-step register loop.
+// Before that, every wave applies panel q-1 to a tile of column q on v_mfma_f64_16x16x4f64; while the factor waves run,
+// 4 "update" waves apply panel q-1 to the remaining trailing tiles (i, j), j > q (ldl_panels).  The 106-pivot chain
+// runs on the factor waves only.
 // Same algebra as the scalar right-looking LDL^T (SparseCholeskyLinearSystemSolver.cpp:48-89 / Cholmod(impl).hpp:
 // 387-399 factor the same matrix); only the accumulation order of the trailing updates differs.
 // ---------------------------------------------------------------------------------------------
@@ -3743,215 +3457,10 @@ __device__ __forceinline__ void tile_sub(const double* src, double* dst, const v
   }
 }
 
-// v_readlane of M doubles of one lane in one asm statement: each value gets its own SGPR pair, so the reads
-// issue back to back and the FMAs that consume them do not wait on one readlane each (separate readlanes are
-// scheduled into one reused SGPR pair under k_solve's SGPR pressure, which serialises them).  L: the lane.
-template <int L>
-__device__ __forceinline__ void rl1(double v0, double& o0) {
-  const unsigned long long b0 = __double_as_longlong(v0);
-  const unsigned l0 = (unsigned)b0, h0 = (unsigned)(b0 >> 32);
-  unsigned sl0, sh0;
-  asm("s_nop 1\nv_readlane_b32 %0, %2, %4\nv_readlane_b32 %1, %3, %4\ns_nop 1"
-      : "=s"(sl0), "=s"(sh0)
-      : "v"(l0), "v"(h0), "i"(L));
-  o0 = __longlong_as_double(((unsigned long long)sh0 << 32) | sl0);
-}
-template <int L>
-__device__ __forceinline__ void rl2(double v0, double v1, double& o0, double& o1) {
-  const unsigned long long b0 = __double_as_longlong(v0);
-  const unsigned l0 = (unsigned)b0, h0 = (unsigned)(b0 >> 32);
-  unsigned sl0, sh0;
-  const unsigned long long b1 = __double_as_longlong(v1);
-  const unsigned l1 = (unsigned)b1, h1 = (unsigned)(b1 >> 32);
-  unsigned sl1, sh1;
-  asm("s_nop 1\nv_readlane_b32 %0, %4, %8\nv_readlane_b32 %1, %5, %8\nv_readlane_b32 %2, %6, %8\nv_readlane_b32 %3, %7, %8\ns_nop 1"
-      : "=s"(sl0), "=s"(sh0), "=s"(sl1), "=s"(sh1)
-      : "v"(l0), "v"(h0), "v"(l1), "v"(h1), "i"(L));
-  o0 = __longlong_as_double(((unsigned long long)sh0 << 32) | sl0);
-  o1 = __longlong_as_double(((unsigned long long)sh1 << 32) | sl1);
-}
-template <int L>
-__device__ __forceinline__ void rl3(double v0, double v1, double v2, double& o0, double& o1, double& o2) {
-  const unsigned long long b0 = __double_as_longlong(v0);
-  const unsigned l0 = (unsigned)b0, h0 = (unsigned)(b0 >> 32);
-  unsigned sl0, sh0;
-  const unsigned long long b1 = __double_as_longlong(v1);
-  const unsigned l1 = (unsigned)b1, h1 = (unsigned)(b1 >> 32);
-  unsigned sl1, sh1;
-  const unsigned long long b2 = __double_as_longlong(v2);
-  const unsigned l2 = (unsigned)b2, h2 = (unsigned)(b2 >> 32);
-  unsigned sl2, sh2;
-  asm("s_nop 1\nv_readlane_b32 %0, %6, %12\nv_readlane_b32 %1, %7, %12\nv_readlane_b32 %2, %8, %12\nv_readlane_b32 %3, %9, %12\nv_readlane_b32 %4, %10, %12\nv_readlane_b32 %5, %11, %12\ns_nop 1"
-      : "=s"(sl0), "=s"(sh0), "=s"(sl1), "=s"(sh1), "=s"(sl2), "=s"(sh2)
-      : "v"(l0), "v"(h0), "v"(l1), "v"(h1), "v"(l2), "v"(h2), "i"(L));
-  o0 = __longlong_as_double(((unsigned long long)sh0 << 32) | sl0);
-  o1 = __longlong_as_double(((unsigned long long)sh1 << 32) | sl1);
-  o2 = __longlong_as_double(((unsigned long long)sh2 << 32) | sl2);
-}
-template <int L>
-__device__ __forceinline__ void rl4(double v0, double v1, double v2, double v3, double& o0, double& o1, double& o2, double& o3) {
-  const unsigned long long b0 = __double_as_longlong(v0);
-  const unsigned l0 = (unsigned)b0, h0 = (unsigned)(b0 >> 32);
-  unsigned sl0, sh0;
-  const unsigned long long b1 = __double_as_longlong(v1);
-  const unsigned l1 = (unsigned)b1, h1 = (unsigned)(b1 >> 32);
-  unsigned sl1, sh1;
-  const unsigned long long b2 = __double_as_longlong(v2);
-  const unsigned l2 = (unsigned)b2, h2 = (unsigned)(b2 >> 32);
-  unsigned sl2, sh2;
-  const unsigned long long b3 = __double_as_longlong(v3);
-  const unsigned l3 = (unsigned)b3, h3 = (unsigned)(b3 >> 32);
-  unsigned sl3, sh3;
-  asm("s_nop 1\nv_readlane_b32 %0, %8, %16\nv_readlane_b32 %1, %9, %16\nv_readlane_b32 %2, %10, %16\nv_readlane_b32 %3, %11, %16\nv_readlane_b32 %4, %12, %16\nv_readlane_b32 %5, %13, %16\nv_readlane_b32 %6, %14, %16\nv_readlane_b32 %7, %15, %16\ns_nop 1"
-      : "=s"(sl0), "=s"(sh0), "=s"(sl1), "=s"(sh1), "=s"(sl2), "=s"(sh2), "=s"(sl3), "=s"(sh3)
-      : "v"(l0), "v"(h0), "v"(l1), "v"(h1), "v"(l2), "v"(h2), "v"(l3), "v"(h3), "i"(L));
-  o0 = __longlong_as_double(((unsigned long long)sh0 << 32) | sl0);
-  o1 = __longlong_as_double(((unsigned long long)sh1 << 32) | sl1);
-  o2 = __longlong_as_double(((unsigned long long)sh2 << 32) | sl2);
-  o3 = __longlong_as_double(((unsigned long long)sh3 << 32) | sl3);
-}
-template <int L>
-__device__ __forceinline__ void rl5(double v0, double v1, double v2, double v3, double v4, double& o0, double& o1, double& o2, double& o3, double& o4) {
-  const unsigned long long b0 = __double_as_longlong(v0);
-  const unsigned l0 = (unsigned)b0, h0 = (unsigned)(b0 >> 32);
-  unsigned sl0, sh0;
-  const unsigned long long b1 = __double_as_longlong(v1);
-  const unsigned l1 = (unsigned)b1, h1 = (unsigned)(b1 >> 32);
-  unsigned sl1, sh1;
-  const unsigned long long b2 = __double_as_longlong(v2);
-  const unsigned l2 = (unsigned)b2, h2 = (unsigned)(b2 >> 32);
-  unsigned sl2, sh2;
-  const unsigned long long b3 = __double_as_longlong(v3);
-  const unsigned l3 = (unsigned)b3, h3 = (unsigned)(b3 >> 32);
-  unsigned sl3, sh3;
-  const unsigned long long b4 = __double_as_longlong(v4);
-  const unsigned l4 = (unsigned)b4, h4 = (unsigned)(b4 >> 32);
-  unsigned sl4, sh4;
-  asm("s_nop 1\nv_readlane_b32 %0, %10, %20\nv_readlane_b32 %1, %11, %20\nv_readlane_b32 %2, %12, %20\nv_readlane_b32 %3, %13, %20\nv_readlane_b32 %4, %14, %20\nv_readlane_b32 %5, %15, %20\nv_readlane_b32 %6, %16, %20\nv_readlane_b32 %7, %17, %20\nv_readlane_b32 %8, %18, %20\nv_readlane_b32 %9, %19, %20\ns_nop 1"
-      : "=s"(sl0), "=s"(sh0), "=s"(sl1), "=s"(sh1), "=s"(sl2), "=s"(sh2), "=s"(sl3), "=s"(sh3), "=s"(sl4), "=s"(sh4)
-      : "v"(l0), "v"(h0), "v"(l1), "v"(h1), "v"(l2), "v"(h2), "v"(l3), "v"(h3), "v"(l4), "v"(h4), "i"(L));
-  o0 = __longlong_as_double(((unsigned long long)sh0 << 32) | sl0);
-  o1 = __longlong_as_double(((unsigned long long)sh1 << 32) | sl1);
-  o2 = __longlong_as_double(((unsigned long long)sh2 << 32) | sl2);
-  o3 = __longlong_as_double(((unsigned long long)sh3 << 32) | sl3);
-  o4 = __longlong_as_double(((unsigned long long)sh4 << 32) | sl4);
-}
-template <int L>
-__device__ __forceinline__ void rl6(double v0, double v1, double v2, double v3, double v4, double v5, double& o0, double& o1, double& o2, double& o3, double& o4, double& o5) {
-  const unsigned long long b0 = __double_as_longlong(v0);
-  const unsigned l0 = (unsigned)b0, h0 = (unsigned)(b0 >> 32);
-  unsigned sl0, sh0;
-  const unsigned long long b1 = __double_as_longlong(v1);
-  const unsigned l1 = (unsigned)b1, h1 = (unsigned)(b1 >> 32);
-  unsigned sl1, sh1;
-  const unsigned long long b2 = __double_as_longlong(v2);
-  const unsigned l2 = (unsigned)b2, h2 = (unsigned)(b2 >> 32);
-  unsigned sl2, sh2;
-  const unsigned long long b3 = __double_as_longlong(v3);
-  const unsigned l3 = (unsigned)b3, h3 = (unsigned)(b3 >> 32);
-  unsigned sl3, sh3;
-  const unsigned long long b4 = __double_as_longlong(v4);
-  const unsigned l4 = (unsigned)b4, h4 = (unsigned)(b4 >> 32);
-  unsigned sl4, sh4;
-  const unsigned long long b5 = __double_as_longlong(v5);
-  const unsigned l5 = (unsigned)b5, h5 = (unsigned)(b5 >> 32);
-  unsigned sl5, sh5;
-  asm("s_nop 1\nv_readlane_b32 %0, %12, %24\nv_readlane_b32 %1, %13, %24\nv_readlane_b32 %2, %14, %24\nv_readlane_b32 %3, %15, %24\nv_readlane_b32 %4, %16, %24\nv_readlane_b32 %5, %17, %24\nv_readlane_b32 %6, %18, %24\nv_readlane_b32 %7, %19, %24\nv_readlane_b32 %8, %20, %24\nv_readlane_b32 %9, %21, %24\nv_readlane_b32 %10, %22, %24\nv_readlane_b32 %11, %23, %24\ns_nop 1"
-      : "=s"(sl0), "=s"(sh0), "=s"(sl1), "=s"(sh1), "=s"(sl2), "=s"(sh2), "=s"(sl3), "=s"(sh3), "=s"(sl4), "=s"(sh4), "=s"(sl5), "=s"(sh5)
-      : "v"(l0), "v"(h0), "v"(l1), "v"(h1), "v"(l2), "v"(h2), "v"(l3), "v"(h3), "v"(l4), "v"(h4), "v"(l5), "v"(h5), "i"(L));
-  o0 = __longlong_as_double(((unsigned long long)sh0 << 32) | sl0);
-  o1 = __longlong_as_double(((unsigned long long)sh1 << 32) | sl1);
-  o2 = __longlong_as_double(((unsigned long long)sh2 << 32) | sl2);
-  o3 = __longlong_as_double(((unsigned long long)sh3 << 32) | sl3);
-  o4 = __longlong_as_double(((unsigned long long)sh4 << 32) | sl4);
-  o5 = __longlong_as_double(((unsigned long long)sh5 << 32) | sl5);
-}
-template <int L>
-__device__ __forceinline__ void rl7(double v0, double v1, double v2, double v3, double v4, double v5, double v6, double& o0, double& o1, double& o2, double& o3, double& o4, double& o5, double& o6) {
-  const unsigned long long b0 = __double_as_longlong(v0);
-  const unsigned l0 = (unsigned)b0, h0 = (unsigned)(b0 >> 32);
-  unsigned sl0, sh0;
-  const unsigned long long b1 = __double_as_longlong(v1);
-  const unsigned l1 = (unsigned)b1, h1 = (unsigned)(b1 >> 32);
-  unsigned sl1, sh1;
-  const unsigned long long b2 = __double_as_longlong(v2);
-  const unsigned l2 = (unsigned)b2, h2 = (unsigned)(b2 >> 32);
-  unsigned sl2, sh2;
-  const unsigned long long b3 = __double_as_longlong(v3);
-  const unsigned l3 = (unsigned)b3, h3 = (unsigned)(b3 >> 32);
-  unsigned sl3, sh3;
-  const unsigned long long b4 = __double_as_longlong(v4);
-  const unsigned l4 = (unsigned)b4, h4 = (unsigned)(b4 >> 32);
-  unsigned sl4, sh4;
-  const unsigned long long b5 = __double_as_longlong(v5);
-  const unsigned l5 = (unsigned)b5, h5 = (unsigned)(b5 >> 32);
-  unsigned sl5, sh5;
-  const unsigned long long b6 = __double_as_longlong(v6);
-  const unsigned l6 = (unsigned)b6, h6 = (unsigned)(b6 >> 32);
-  unsigned sl6, sh6;
-  asm("s_nop 1\nv_readlane_b32 %0, %14, %28\nv_readlane_b32 %1, %15, %28\nv_readlane_b32 %2, %16, %28\nv_readlane_b32 %3, %17, %28\nv_readlane_b32 %4, %18, %28\nv_readlane_b32 %5, %19, %28\nv_readlane_b32 %6, %20, %28\nv_readlane_b32 %7, %21, %28\nv_readlane_b32 %8, %22, %28\nv_readlane_b32 %9, %23, %28\nv_readlane_b32 %10, %24, %28\nv_readlane_b32 %11, %25, %28\nv_readlane_b32 %12, %26, %28\nv_readlane_b32 %13, %27, %28\ns_nop 1"
-      : "=s"(sl0), "=s"(sh0), "=s"(sl1), "=s"(sh1), "=s"(sl2), "=s"(sh2), "=s"(sl3), "=s"(sh3), "=s"(sl4), "=s"(sh4), "=s"(sl5), "=s"(sh5), "=s"(sl6), "=s"(sh6)
-      : "v"(l0), "v"(h0), "v"(l1), "v"(h1), "v"(l2), "v"(h2), "v"(l3), "v"(h3), "v"(l4), "v"(h4), "v"(l5), "v"(h5), "v"(l6), "v"(h6), "i"(L));
-  o0 = __longlong_as_double(((unsigned long long)sh0 << 32) | sl0);
-  o1 = __longlong_as_double(((unsigned long long)sh1 << 32) | sl1);
-  o2 = __longlong_as_double(((unsigned long long)sh2 << 32) | sl2);
-  o3 = __longlong_as_double(((unsigned long long)sh3 << 32) | sl3);
-  o4 = __longlong_as_double(((unsigned long long)sh4 << 32) | sl4);
-  o5 = __longlong_as_double(((unsigned long long)sh5 << 32) | sl5);
-  o6 = __longlong_as_double(((unsigned long long)sh6 << 32) | sl6);
-}
-
-// row[J0 .. J0 + M - 1] of lane L into bc[] (M <= 7: one asm statement)
-template <int L, int J0, int M>
-__device__ __forceinline__ void rl_chunk(const double (&row)[16], double (&bc)[16]) {
-  if constexpr (M == 1) rl1<L>(row[J0], bc[J0]);
-  else if constexpr (M == 2) rl2<L>(row[J0], row[J0 + 1], bc[J0], bc[J0 + 1]);
-  else if constexpr (M == 3) rl3<L>(row[J0], row[J0 + 1], row[J0 + 2], bc[J0], bc[J0 + 1], bc[J0 + 2]);
-  else if constexpr (M == 4)
-    rl4<L>(row[J0], row[J0 + 1], row[J0 + 2], row[J0 + 3], bc[J0], bc[J0 + 1], bc[J0 + 2], bc[J0 + 3]);
-  else if constexpr (M == 5)
-    rl5<L>(row[J0], row[J0 + 1], row[J0 + 2], row[J0 + 3], row[J0 + 4], bc[J0], bc[J0 + 1], bc[J0 + 2], bc[J0 + 3],
-           bc[J0 + 4]);
-  else if constexpr (M == 6)
-    rl6<L>(row[J0], row[J0 + 1], row[J0 + 2], row[J0 + 3], row[J0 + 4], row[J0 + 5], bc[J0], bc[J0 + 1], bc[J0 + 2],
-           bc[J0 + 3], bc[J0 + 4], bc[J0 + 5]);
-  else
-    rl7<L>(row[J0], row[J0 + 1], row[J0 + 2], row[J0 + 3], row[J0 + 4], row[J0 + 5], row[J0 + 6], bc[J0], bc[J0 + 1],
-           bc[J0 + 2], bc[J0 + 3], bc[J0 + 4], bc[J0 + 5], bc[J0 + 6]);
-}
-// row[J0 .. 15] of lane L into bc[], chunks of 7
-template <int L, int J0>
-__device__ __forceinline__ void rl_tail(const double (&row)[16], double (&bc)[16]) {
-  if constexpr (J0 < 16) {
-    constexpr int M = (16 - J0) < 7 ? (16 - J0) : 7;
-    rl_chunk<L, J0, M>(row, bc);
-    rl_tail<L, J0 + M>(row, bc);
-  }
-}
-
 // 1/x by v_rcp_f64 + one Newton step (the pivot chain of the panel factorisation: one FMA pair shorter)
 __device__ __forceinline__ double recip_d1(double x) {
   const double r = __builtin_amdgcn_rcp(x);
   return fma(r, fma(-x, r, 1.0), r);
-}
-
-// pivot steps K .. 15 of the lane-row panel factorisation (row k of the trailing matrix broadcast from lane k).
-// Every lane applies f = row[k] / D_k: lanes above the pivot hold zeros right of their own pivot (their own step
-// cancelled them: f = 1 against their own row), so no lane mask sits in the pivot chain.
-template <int K>
-__device__ __forceinline__ void panel_steps(double (&row)[16], int lane, int q, int C, bool& ok, double& rd) {
-  if constexpr (K < 16) {
-    double bc[16];
-    rl_tail<K, K>(row, bc);  // bc[K] = D_K, bc[j] = S[K][j] (reading D_K on its own first measured no faster)
-    const double Dk = bc[K];
-    const double rdk = Dk > 0.0 ? recip_d1(Dk) : 0.0;
-    const double f = row[K] * rdk;
-#pragma unroll
-    for (int j = K + 1; j < 16; ++j) row[j] -= f * bc[j];
-    ok = ok & ((Dk > 0.0) | (16 * q + K >= C));  // bitwise: no branch per pivot
-    rd = (lane == K) ? rdk : rd;
-    panel_steps<K + 1>(row, lane, q, C, ok, rd);
-  }
 }
 
 // x += (lane L's y within the lane's 16-lane row) * f: one v_fmac_f64 whose src0 is read through DPP row_newbcast:L
@@ -4003,27 +3512,14 @@ __device__ __forceinline__ void panel2_cols(double (&dr)[16], double (&br)[16], 
 // entries from lane K of the lane's own 16-lane row, by DPP row_newbcast fused into the FMAs (no v_readlane / SGPR hop,
 // no LDS round trip).  Lanes above the pivot hold zeros right of their own pivot (their own step cancelled them), so no
 // lane mask sits in the pivot chain.
-template <int K>
-__device__ __forceinline__ void panel2_steps(double (&dr)[16], double (&br)[16], int r, int q, int C, bool& ok,
-                                             double& rd) {
-  if constexpr (K < 16) {
-    // D_K from lane K (its row's pivot), with the DPP wait inside the statement: dr[K] may have been written by the
-    // previous step's last FMA just before (K = 15); every later DPP read of this step follows it
-    const double Dk = bcast16_dep<K>(dr[K]);
-    const double rdk = Dk > 0.0 ? recip_d1(Dk) : 0.0;
-    const double nfd = -(dr[K] * rdk), nfb = -(br[K] * rdk);
-    panel2_cols<K, K + 1>(dr, br, nfd, nfb);
-    ok = ok & ((Dk > 0.0) | (16 * q + K >= C));  // bitwise: no branch per pivot
-    rd = (r == K) ? rdk : rd;
-    panel2_steps<K + 1>(dr, br, r, q, C, ok, rd);
-  }
-}
-
-// panel2_steps with a one-step lookahead: step K's column K + 1 first, then step K + 1's pivot (D_{K+1} by DPP, the
-// reciprocal, its multipliers), then step K's columns K + 2 .. 15, so that the pivot's broadcast -> v_rcp -> Newton
-// chain issues while the bulk of step K's FMAs is still in the wave's stream (in-order issue: without the lookahead
-// every pivot waits behind the previous step's 2 (15 - K) FMAs).  Same operations and operands per entry as
-// panel2_steps: bitwise the same factor.  nfd / nfb: step K's multipliers (computed by the caller / the previous step).
+// With a one-step lookahead: step K's column K + 1 first, then step K + 1's pivot (D_{K+1} by DPP, the reciprocal, its
+// multipliers), then step K's columns K + 2 .. 15, so that the pivot's broadcast -> v_rcp -> Newton chain issues while
+// the bulk of step K's FMAs is still in the wave's stream (in-order issue: without the lookahead every pivot waits
+// behind the previous step's 2 (15 - K) FMAs).  Each entry takes the operations and operands of the step-by-step
+// order.  nfd / nfb: step K's multipliers (computed by the caller / the previous step).  D_{K+1} is read with the DPP
+// wait inside the statement (bcast16_dep): dr[K + 1] was written by the FMA just before.
+// (Two pivots at a time through their 2 x 2 block, 8 reciprocal chains instead of 16, measured slower: the factor wave
+// is issue-bound and the block form adds ~40 VALU per pivot pair, configs[3] pass 0.1237 -> 0.1300 ms)
 template <int K>
 __device__ __forceinline__ void panel3_steps(double (&dr)[16], double (&br)[16], int r, int q, int C, bool& ok,
                                              double& rd, double nfd, double nfb) {
@@ -4039,67 +3535,6 @@ __device__ __forceinline__ void panel3_steps(double (&dr)[16], double (&br)[16],
       rd = (r == K + 1) ? rdn : rd;
       panel3_steps<K + 1>(dr, br, r, q, C, ok, rd, nfdn, nfbn);
     }
-  }
-}
-
-// the same after 2 wait states (its DPP source was written by the previous VALU instruction)
-template <int L>
-__device__ __forceinline__ void fmac_bc_self_dep(double& x, double f) {
-  asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf"
-               : "+v"(x) : "v"(f), "i"(L));
-}
-
-// columns J .. 15 of a 2 x 2 pivot step (panel4_steps): per column the below row from the ORIGINAL pivot rows K, K + 1
-// (DPP reads before the diagonal rows change), then the diagonal row's step-K part; its step-(K + 1) part is issued
-// after the next column's below-row updates, so that its DPP read of the register the step-K part just wrote has its
-// two wait states without an s_nop (the pivot lanes' own values move by rounding only: their multipliers are 1 / 0 up
-// to rounding, and they are never read again as pivot rows)
-template <int K, int J>
-__device__ __forceinline__ void panel4_cols(double (&dr)[16], double (&br)[16], double nd1, double nd2, double nb1,
-                                            double nb2) {
-  if constexpr (J < 16) {
-    fmac_bc<K>(br[J], dr[J], nb1);
-    fmac_bc<K + 1>(br[J], dr[J], nb2);
-    if constexpr (J > K + 2) fmac_bc_self<K + 1>(dr[J - 1], nd2);
-    fmac_bc_self<K>(dr[J], nd1);
-    if constexpr (J == 15) fmac_bc_self_dep<K + 1>(dr[15], nd2);
-    panel4_cols<K, J + 1>(dr, br, nd1, nd2, nb1, nb2);
-  }
-}
-
-// (KB_PANEL_2X2, not the default: the factor wave is issue-bound, ~7 cycles per f64 FMA of one wave, on the 240 column
-// FMAs per lane of a panel (2 rows x 120), and the block form's three reciprocal chains and multiplier selects add ~40 VALU per pivot
-// pair: 16 pivots 1.0 -> 1.5 us.)  The panel factorisation two pivots at a time: pivots K, K + 1 eliminated together
-// through the 2 x 2 block
-// [[a, b], [b, c]] (rows K, K + 1 from lanes K, K + 1 by DPP): one reciprocal chain per two pivots (1/a, 1/det and 1/c
-// are independent), so the pivot chain of a panel is 8 steps instead of 16.  A lane's multipliers are its two entries
-// times the block inverse, [f1 f2] = [x_K x_K+1] B^-1, and column K + 1 takes the step-K part only, so the factor is
-// the sequential one's (the W = L D form, D on the diagonal, 1/D in rd) up to rounding; when a pivot fails the
-// multipliers follow the sequential semantics (a <= 0: step K skipped, c alone; det <= 0: step K + 1 skipped).
-template <int K>
-__device__ __forceinline__ void panel4_steps(double (&dr)[16], double (&br)[16], int r, int q, int C, bool& ok,
-                                             double& rd) {
-  if constexpr (K < 16) {
-    const double a = bcast16_dep<K>(dr[K]);
-    const double b = bcast16_dep<K>(dr[K + 1]);
-    const double c = bcast16_dep<K + 1>(dr[K + 1]);
-    const double det = fma(a, c, -(b * b));
-    const bool pa = a > 0.0, pd = pa && det > 0.0, pc = c > 0.0;
-    const double rda = pa ? recip_d1(a) : 0.0;
-    const double rdt = pd ? recip_d1(det) : 0.0;
-    const double rc = pc ? recip_d1(c) : 0.0;
-    // B^-1 with the sequential semantics of failed pivots
-    const double i11 = pd ? c * rdt : rda, i12 = pd ? -(b * rdt) : 0.0, i22 = pd ? a * rdt : (pa ? 0.0 : rc);
-    const double xd0 = dr[K], xd1 = dr[K + 1], xb0 = br[K], xb1 = br[K + 1];
-    const double nd1 = -fma(xd0, i11, xd1 * i12), nd2 = -fma(xd0, i12, xd1 * i22);
-    const double nb1 = -fma(xb0, i11, xb1 * i12), nb2 = -fma(xb0, i12, xb1 * i22);
-    // column K + 1: the step-K update only (W form: W[j][K + 1] = S[j][K + 1] - S[j][K] b / a, D_{K+1} on lane K + 1)
-    br[K + 1] = fma(-(xb0 * rda), b, xb1);
-    dr[K + 1] = fma(-(xd0 * rda), b, xd1);
-    panel4_cols<K, K + 2>(dr, br, nd1, nd2, nb1, nb2);
-    ok = ok & (pa | (16 * q + K >= C)) & ((pa ? pd : pc) | (16 * q + K + 1 >= C));  // bitwise: no branch per pivot
-    rd = (r == K) ? rda : ((r == K + 1) ? (pa ? a * rdt : rc) : rd);
-    panel4_steps<K + 2>(dr, br, r, q, C, ok, rd);
   }
 }
 
@@ -4124,11 +3559,6 @@ __device__ __forceinline__ bool panel_factor2(const KbDev& d, double* S, double*
   bool ok = true;
   double rd = 1.0;
   if (q == 2 && fw == 0) KB_TS(d, 41);
-#ifdef KB_PANEL_NOLOOK
-  panel2_steps<0>(dr, br, r, q, C, ok, rd);
-#elif defined(KB_PANEL_2X2)  // measured slower (configs[3] pass 0.1237 -> 0.1300 ms): see DESIGN.md 9
-  panel4_steps<0>(dr, br, r, q, C, ok, rd);
-#else
   {
     const double D0 = bcast16_dep<0>(dr[0]);
     const double rd0 = D0 > 0.0 ? recip_d1(D0) : 0.0;
@@ -4136,7 +3566,6 @@ __device__ __forceinline__ bool panel_factor2(const KbDev& d, double* S, double*
     rd = (r == 0) ? rd0 : rd;
     panel3_steps<0>(dr, br, r, q, C, ok, rd, -(dr[0] * rd0), -(br[0] * rd0));
   }
-#endif
 #ifdef KB_STAMPS
 #pragma unroll
   for (int c = 0; c < 16; ++c) KB_KEEP(br[c]);
@@ -4156,70 +3585,10 @@ __device__ __forceinline__ bool panel_factor2(const KbDev& d, double* S, double*
   return ok;
 }
 
-// panel q by factor wave fw (rows in registers, one per lane: lanes 0..15 the diagonal tile, lanes 16..63 the rows of
-// tiles q+1+3fw .. q+3+3fw).  The tiles of column q are complete (every earlier panel applied).  W rows go back in
-// place, the factored diagonal tile (W strictly below, D on the diagonal) to Dfac (wave 0), 1/D to rD.  Returns false
-// on a non-positive pivot of a real row (< C); the b row's pivot and the identity padding are not tested.
-__device__ __forceinline__ bool panel_factor(const KbDev& d, double* S, double* rD, double* Dfac, int q, int nb, int C,
-                                             int fw) {
-  const int lane = threadIdx.x & 63, r = lane & 15, t = lane >> 4;
-  const int ti_raw = q + 3 * fw + t;
-  const bool live = t == 0 || ti_raw < nb;
-  // the lane's row (diagonal tiles are whole, so every lane reads 16 consecutive entries)
-  double* base = S + tile_base(t == 0 ? q : (live ? ti_raw : q), q) + r * kTS;
-  double row[16];
-#pragma unroll
-  for (int c = 0; c < 16; ++c) row[c] = base[c];
-  bool ok = true;
-  double rd = 1.0;
-#ifdef KB_STAMPS
-#pragma unroll
-  for (int c = 0; c < 16; ++c) KB_KEEP(row[c]);
-#endif
-  if (q == 2 && fw == 0) KB_TS(d, 41);
-  panel_steps<0>(row, lane, q, C, ok, rd);  // (row K through LDS instead of readlanes: 16 steps 1.36 -> 2.72 us)
-#ifdef KB_STAMPS
-#pragma unroll
-  for (int c = 0; c < 16; ++c) KB_KEEP(row[c]);
-  KB_KEEP(rd);
-#endif
-  if (q == 2 && fw == 0) KB_TS(d, 42);
-  if (t > 0 && live) {
-#pragma unroll
-    for (int c = 0; c < 16; ++c) base[c] = row[c];
-  } else if (t == 0 && fw == 0) {
-    double* dd = Dfac + q * kTileSz + r * kTS;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) dd[c] = row[c];
-    rD[16 * q + r] = rd;
-  }
-  return ok;
-}
-
 // X = Ltilde_tt^-1 of factored diagonal tile t (unit lower, Ltilde = W D^-1) into Xinv[t] (row-major, stride kTS), by
 // one wave: lane (g, r) holds X[r][4g .. 4g+3]; step m subtracts L[r][m] X[m][:] from the rows r > m, X[m] broadcast
-// within each 16-lane group by DPP (off the factorisation's critical path: the backsolve's tile mat-vecs use it)
-__device__ __forceinline__ void tile_unit_inverse(const double* Dfac, const double* rD, double* Xinv, int t) {
-  const int lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
-  const double* Lr = Dfac + t * kTileSz + r * kTS;
-  double L[16];
-#pragma unroll
-  for (int m = 0; m < 16; ++m) L[m] = (m < r) ? Lr[m] * rD[16 * t + m] : 0.0;
-  double X[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) X[j] = (4 * g + j == r) ? 1.0 : 0.0;
-#pragma unroll
-  for (int m = 0; m < 15; ++m) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) X[j] = fma(-L[m], bcast16(X[j], m), X[j]);
-  }
-  double* xo = Xinv + t * kTileSz + r * kTS + 4 * g;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) xo[j] = X[j];
-}
-
-// tile_unit_inverse with the broadcasts fused into the FMAs (DPP row_newbcast source operand): 60 dependent-free FMAs
-// per lane in 15 steps of 4 independent columns
+// within each 16-lane group by DPP row_newbcast fused into the FMAs: 60 dependent-free FMAs per lane in 15 steps of 4
+// independent columns (off the factorisation's critical path: the backsolve's tile mat-vecs use it)
 template <int M>
 __device__ __forceinline__ void tui_steps(double (&X)[4], const double (&nL)[16]) {
   if constexpr (M < 15) {
@@ -4248,7 +3617,7 @@ __device__ __forceinline__ void tile_unit_inverse2(const double* Dfac, const dou
 
 // the factorisation (every thread of the 8-wave block calls it); two phases per panel q:
 //   A (q > 0): column q of the trailing matrix gets panel q-1 (tiles (q + w, q), one per wave w, on MFMA);
-//   B: factor waves 0 (and 1 while panel q has more than three tiles below it) factor panel q; update waves 2, 3, 6, 7
+//   B: factor waves 0 (and 1 while panel q has more than four tiles below it) factor panel q; update waves 2, 3, 6, 7
 //      apply panel q-1 to the remaining trailing tiles (i, j), j > q (waves 4 and 5 share the factor waves' SIMDs and
 //      stay idle so that the MFMA tiles do not slow the pivot chain); wave 7 then inverts the previous panel's factored
 //      diagonal tile (Xinv, for the backsolve's mat-vecs).
@@ -4267,18 +3636,10 @@ __device__ __forceinline__ void ldl_panels(const KbDev& d, double* S, double* rD
       }
       __syncthreads();
     }
-#ifdef KB_PANEL_READLANE
-    const int nf = (nb - 1 - q) > 3 ? 2 : 1;  // the readlane panel: 3 tiles below per factor wave
-#else
-    const int nf = (nb - 1 - q) > 4 ? 2 : 1;  // the DPP panel: 4 tiles below per factor wave
-#endif
+    const int nf = (nb - 1 - q) > 4 ? 2 : 1;  // 4 tiles below per factor wave
     if (wave < nf) {
       if (wave == 0) KB_TS(d, 20 + 2 * q);
-#ifdef KB_PANEL_READLANE
-      const bool ok = panel_factor(d, S, rD, Dfac, q, nb, C, wave);
-#else
       const bool ok = panel_factor2(d, S, rD, Dfac, q, nb, C, wave);
-#endif
       if (wave == 0) {
         if (!ok && lane == 0) *okl = 0;
         KB_WAVE_SYNC();
@@ -4327,7 +3688,7 @@ __device__ __forceinline__ void ldl_panels(const KbDev& d, double* S, double* rD
       // the factored diagonal tiles' inverses for the backsolve on SIMD 1, idle once panel q has one factor wave
       // (q >= 2 for C <= 111): tile t at panel t + 2 on wave 1, the last one (t = nb - 2) at the last panel on wave 5;
       // the last tile, holding row C, is solved by its chain
-      // (while wave 1 still factors, i.e. nf == 2 in the readlane variant, wave 5 takes tile q - 2)
+      // (while wave 1 still factors, nf == 2, wave 5 takes tile q - 2: not reached for nb <= 7, nf == 1 from q = 2 on)
       const int t = (wave == 1 || nf == 2) ? q - 2 : (q == nb - 1 ? nb - 2 : -1);
       if (t >= 0) tile_unit_inverse2(Dfac, rD, Xinv, t);
     }
@@ -4336,67 +3697,8 @@ __device__ __forceinline__ void ldl_panels(const KbDev& d, double* S, double* rD
   }
 }
 
-// one tile ti of the backsolve (panel_backsolve).  CHAIN: the tile's own triangle by 16 dependent DPP steps (the
-// last tile: its rows from C on are masked, and no inverse of it exists); otherwise by the precomputed inverse
-// X = Ltilde_tt^-1: x_t[r] = sum_{c >= r} X[c][r] y[c], 16 independent products (two accumulators).  Then the tile's
-// final values go to every lane through pub, which subtracts them from the rows of the earlier tiles.
-template <bool CHAIN>
-__device__ __forceinline__ void bs_tile(const double* S, const double* Dfac, const double* Xinv, int C, int ti,
-                                        const int (&row)[2], const double (&rdv)[2], double* pub, double (&x)[2]) {
-  const int lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
-  const int tg = ti & 3, ts = ti >> 2, i0 = 16 * ti;
-  double M[16], Le[2][16];
-  const double* pm = (CHAIN ? Dfac : Xinv) + ti * kTileSz + r;  // column r of the factored tile / of its inverse
-#pragma unroll
-  for (int u = 0; u < 16; ++u) M[u] = pm[u * kTS];
-  // rows of the earlier tiles: Ltilde[i0 + u][row] (row < i0; other lanes read a valid tile and discard it)
-#pragma unroll
-  for (int sl = 0; sl < 2; ++sl) {
-    const double* pe = S + tile_base(ti, min(row[sl] >> 4, ti)) + (row[sl] & 15);
-#pragma unroll
-    for (int u = 0; u < 16; ++u) Le[sl][u] = pe[u * kTS];
-  }
-  double xt = ts ? x[1] : x[0];
-  const int lim = C - i0;  // rows of this tile below C (CHAIN only; the other tiles are whole)
-  if constexpr (CHAIN) {
-    const double rdt = ts ? rdv[1] : rdv[0];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) M[u] = (r < u && u < lim) ? M[u] * rdt : 0.0;
-#pragma unroll
-    for (int u = 15; u >= 0; --u) xt = fma(-M[u], bcast16(xt, u), xt);
-  } else {
-    double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-    for (int c = 0; c < 16; c += 2) {
-      a0 = fma(c >= r ? M[c] : 0.0, bcast16(xt, c), a0);
-      a1 = fma(c + 1 >= r ? M[c + 1] : 0.0, bcast16(xt, c + 1), a1);
-    }
-    xt = a0 + a1;
-  }
-  if (g == tg) {
-    if (ts) x[1] = xt;
-    else x[0] = xt;
-    pub[r] = xt;
-  }
-  KB_WAVE_SYNC();
-  double xp[16];
-#pragma unroll
-  for (int u = 0; u < 16; ++u) xp[u] = (!CHAIN || u < lim) ? pub[u] : 0.0;
-#pragma unroll
-  for (int sl = 0; sl < 2; ++sl) {
-    double acc = 0.0;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) acc = fma(Le[sl][u], xp[u], acc);
-    if (row[sl] < i0) x[sl] -= acc * rdv[sl];
-  }
-  KB_WAVE_SYNC();  // pub is rewritten by the next tile
-}
-
-// x = Ltilde^-T z, z = (row C of the factor) D^-1, by one wave.  Lane l = 16 g + r holds the rows 16 (g + 4 s) + r,
-// s = 0, 1: tile t lives in the 16-lane group t & 3, slot t >> 2.  Tiles from the last (bs_tile); the result comes
-// back in x[s] = x_{l + 64 s}.
-// Once tile pub_tile is done (xb != nullptr), the final x of rows >= 16 pub_tile go to xb[] and *bflag is set: the
-// baseline columns, for the wave that updates the baselines and builds the camera chains meanwhile.
+// the backsolve (panel_backsolve2), once tile pub_tile is done: the final x of rows >= 16 pub_tile go to xb[] and *bflag
+// is set: the baseline columns, for the wave that updates the baselines and builds the camera chains meanwhile.
 __device__ __forceinline__ void bs_publish(int C, int pub_tile, double* xb, volatile int* bflag, const double (&x)[2]) {
   const int lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
 #pragma unroll
@@ -4408,38 +3710,15 @@ __device__ __forceinline__ void bs_publish(int C, int pub_tile, double* xb, vola
   if (lane == 0) *bflag = 1;
 }
 
-__device__ __forceinline__ void panel_backsolve(const KbDev& d, const double* S, const double* Dfac, const double* Xinv,
-                                                const double* rD, int C, int nb, double* pub, double (&x)[2],
-                                                int pub_tile = -1, double* xb = nullptr, volatile int* bflag = nullptr) {
-  const int lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
-  int row[2];
-  double rdv[2];
-#pragma unroll
-  for (int sl = 0; sl < 2; ++sl) {
-    row[sl] = 16 * (g + 4 * sl) + r;
-    const int rc = min(row[sl], C - 1);
-    // row C's W: in place off the diagonal tile, in Dfac inside it
-    const double* zp = (rc >> 4) == (C >> 4) ? Dfac + (C >> 4) * kTileSz + (C & 15) * kTS + (rc & 15) : S + tidx(C, rc);
-    const double z = *zp, rd = rD[rc];
-    rdv[sl] = rd;
-    x[sl] = row[sl] < C ? z * rd : 0.0;
-  }
-  int ti = (C - 1) >> 4;
-  if (ti == nb - 1) {
-    bs_tile<true>(S, Dfac, Xinv, C, ti, row, rdv, pub, x);  // the tile holding row C
-    if (xb && ti == pub_tile) bs_publish(C, pub_tile, xb, bflag, x);
-    --ti;
-  }
-#pragma unroll 1
-  for (; ti >= 0; --ti) {
-    bs_tile<false>(S, Dfac, Xinv, C, ti, row, rdv, pub, x);
-    if (xb && ti == pub_tile) bs_publish(C, pub_tile, xb, bflag, x);
-  }
-}
-
-// ---- the backsolve with DPP-fused broadcasts (panel_backsolve2): the tile's mat-vec and its dependent chain take their
-// broadcasts through DPP fused into the FMAs, and the tile's values reach the other 16-lane groups through one LDS slot
-// without a wave-wide wait (one wave's LDS accesses complete in order).
+// ---- the backsolve (panel_backsolve2): x = Ltilde^-T z, z = (row C of the factor) D^-1, by one wave.  Lane
+// l = 16 g + r holds the rows 16 (g + 4 s) + r, s = 0, 1: tile t lives in the 16-lane group t & 3, slot t >> 2.  Tiles
+// from the last; the result comes back in x[s] = x_{l + 64 s}.
+// One tile (bs2_load, bs2_solve).  CHAIN: the tile's own triangle by 16 dependent DPP steps (the last tile: its rows
+// from C on are masked, and no inverse of it exists); otherwise by the precomputed inverse X = Ltilde_tt^-1:
+// x_t[r] = sum_{c >= r} X[c][r] y[c], 16 independent products (two accumulators).  The mat-vec and the dependent chain
+// take their broadcasts through DPP fused into the FMAs.  Then the tile's final values reach the other 16-lane groups
+// through one LDS slot (pub) without a wave-wide wait (one wave's LDS accesses complete in order), and every lane
+// subtracts them from the rows of the earlier tiles.
 struct BsOps {
   double M[16];       // column r of X_ti = Ltilde_tt^-1 (CHAIN: of the factored tile), masked to the entries it uses
   double Le[2][16];   // Ltilde[16 ti + u][row[sl]] for the lane's rows (slots 0, 1)
@@ -4548,130 +3827,6 @@ __device__ __forceinline__ void panel_backsolve2(const KbDev& d, const double* S
     bs2_solve<false>(A, C, ti, row, rdv, pub, x);
     if (xb && ti == pub_tile) bs_publish(C, pub_tile, xb, bflag, x);
   }
-}
-
-// ---- the replicated backsolve (panel_backsolve3, measured and not kept: KB_BACKSOLVE3): every 16-lane row of the
-// wave runs the whole
-// backward solve, lane (g, r) holding y_t[r] (row 16 t + r) of every tile t.  Tile t's values then reach the rows of
-// the earlier tiles by DPP row_newbcast inside the lane's own 16-lane row: no LDS publication and no cross-row move.
-// The solve is a fixed sequence of ops, each 16 DPP-fused FMAs over one column of a tile: op (T, T) forms x_T (the
-// mat-vec X_T^T y_T, or the last tile's dependent chain), ops (T, s), s = T-1 .. 0, update y_s by x_T.  Each op's 16
-// operands are loaded from LDS before the previous op's FMAs issue (inline asm is a scheduling boundary, so the
-// prefetch is written out), and masks are multiplications so that no load becomes conditional.  On one CU
-// (tools/micro/camera_solve) it takes 4.7 us with a warm instruction cache and 8.4 us cold (its ~6 KB of straight-line
-// code runs once per launch), against 3.4 us for panel_backsolve2's tile loop either way.
-struct Bs3 {
-  const KbDev* d;  // diagnostic stamps only
-  const double* S;
-  const double* Dfac;
-  const double* Xinv;
-  int C, nb, r;
-};
-
-// operand column of op (T, SS): column r of X_T (the unit-lower tile inverse, exact zeros above its diagonal) or, for
-// the last tile (its chain), of the factored diagonal tile; of tile (T, SS) for an update
-template <int T, int SS>
-__device__ __forceinline__ void bs3_load(const Bs3& b, double (&w)[16]) {
-  const double* pe = (SS == T ? ((T == b.nb - 1) ? b.Dfac : b.Xinv) + T * kTileSz : b.S + tile_base(T, SS)) + b.r;
-#pragma unroll
-  for (int u = 0; u < 16; ++u) w[u] = pe[u * kTS];
-}
-
-template <int T, int SS, int P>
-__device__ __forceinline__ void bs3_op(const Bs3& b, double (&y)[8], const double (&rdv)[8], double& xt,
-                                       double (&w0)[16], double (&w1)[16], int pub_tile, double* xb,
-                                       volatile int* bflag) {
-  if constexpr (T >= 0) {
-    double(&w)[16] = P ? w1 : w0;   // this op's operands (loaded by the previous op)
-    double(&wn)[16] = P ? w0 : w1;  // the next op's
-    constexpr int NT = SS > 0 ? T : T - 1, NS = SS > 0 ? SS - 1 : T - 1;
-    if constexpr (NT >= 0) bs3_load<NT, NS>(b, wn);
-    if constexpr (SS == T) {
-      const int r = b.r, lim = b.C - 16 * T;
-      KB_TS(*b.d, 240 + T);
-      xt = y[T];
-      if (T == b.nb - 1) {  // wave-uniform: the tile holding row C, solved by its dependent chain (rows >= C: x = 0)
-        double M[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) M[u] = -(w[u] * rdv[T]) * ((r < u && u < lim) ? 1.0 : 0.0);
-        // x[r] -= sum_{u > r} L[u][r] x[u], u from the last: 16 dependent steps, x[u] read from lane u by DPP
-#define KB_BS3_STEP(U) fmac_bc_dep<U>(xt, xt, M[U]);
-        KB_BS3_STEP(15) KB_BS3_STEP(14) KB_BS3_STEP(13) KB_BS3_STEP(12) KB_BS3_STEP(11) KB_BS3_STEP(10)
-        KB_BS3_STEP(9) KB_BS3_STEP(8) KB_BS3_STEP(7) KB_BS3_STEP(6) KB_BS3_STEP(5) KB_BS3_STEP(4) KB_BS3_STEP(3)
-        KB_BS3_STEP(2) KB_BS3_STEP(1) KB_BS3_STEP(0)
-#undef KB_BS3_STEP
-      } else {
-        // x_t[r] = sum_{c >= r} X[c][r] y[c] (X lower: the c < r terms are exact zeros), y[c] from lane c by DPP
-        double a0 = 0.0, a1 = 0.0;
-        fmac_bc_dep<0>(a0, xt, w[0]);
-        fmac_bc<1>(a1, xt, w[1]);
-#define KB_BS3_MV(U) fmac_bc<U>(a0, xt, w[U]); fmac_bc<U + 1>(a1, xt, w[U + 1]);
-        KB_BS3_MV(2) KB_BS3_MV(4) KB_BS3_MV(6) KB_BS3_MV(8) KB_BS3_MV(10) KB_BS3_MV(12) KB_BS3_MV(14)
-#undef KB_BS3_MV
-        xt = a0 + a1;
-      }
-      y[T] = xt;
-      if (xb && T == pub_tile) {  // the baseline rows are final: publish them for the baseline / chain wave
-        if ((threadIdx.x & 63) < 16) {
-#pragma unroll
-          for (int t = T; t < 8; ++t)
-            if (t < b.nb && 16 * t + r < b.C) xb[16 * t + r] = y[t];
-        }
-        KB_WAVE_SYNC();
-        if ((threadIdx.x & 63) == 0) *bflag = 1;
-      }
-    } else {
-      // y_s[r] -= (1/D of row 16 s + r) sum_u W[16 T + u][16 s + r] x_T[u], x_T[u] from lane u by DPP (rows >= C of the
-      // last tile carry x = 0)
-      double a0 = 0.0, a1 = 0.0;
-      if constexpr (SS == T - 1) fmac_bc_dep<0>(a0, xt, w[0]);
-      else fmac_bc<0>(a0, xt, w[0]);
-      fmac_bc<1>(a1, xt, w[1]);
-#define KB_BS3_MV(U) fmac_bc<U>(a0, xt, w[U]); fmac_bc<U + 1>(a1, xt, w[U + 1]);
-      KB_BS3_MV(2) KB_BS3_MV(4) KB_BS3_MV(6) KB_BS3_MV(8) KB_BS3_MV(10) KB_BS3_MV(12) KB_BS3_MV(14)
-#undef KB_BS3_MV
-      y[SS] -= (a0 + a1) * rdv[SS];
-    }
-    bs3_op<NT, NS, 1 - P>(b, y, rdv, xt, w0, w1, pub_tile, xb, bflag);
-  }
-}
-
-// entry at the last tile T = nb - 1 (nb in 5..7 for 64 < C <= 111)
-template <int T>
-__device__ __forceinline__ void bs3_run(const Bs3& b, double (&y)[8], const double (&rdv)[8], int pub_tile, double* xb,
-                                        volatile int* bflag) {
-  double w0[16], w1[16], xt = 0.0;
-  bs3_load<T, T>(b, w0);
-  bs3_op<T, T, 0>(b, y, rdv, xt, w0, w1, pub_tile, xb, bflag);
-}
-
-// x = Ltilde^-T z as panel_backsolve (same operands, same result layout: x[s] = x_{l + 64 s}), nb <= 7
-__device__ __forceinline__ void panel_backsolve3(const KbDev& d, const double* S, const double* Dfac, const double* Xinv,
-                                                 const double* rD, int C, int nb, double (&x)[2], int pub_tile = -1,
-                                                 double* xb = nullptr, volatile int* bflag = nullptr) {
-  const int lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
-  Bs3 b{&d, S, Dfac, Xinv, C, nb, r};
-  double y[8], rdv[8];
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const int row = 16 * t + r, rc = min(row, C - 1);
-    // row C's W: in place off the diagonal tile, in Dfac inside it
-    const double* zp = (rc >> 4) == (C >> 4) ? Dfac + (C >> 4) * kTileSz + (C & 15) * kTS + (rc & 15) : S + tidx(C, rc);
-    const double z = *zp, rd = rD[rc];
-    rdv[t] = rd;
-    y[t] = (t < nb && row < C) ? z * rd : 0.0;
-  }
-  if (nb == 7) bs3_run<6>(b, y, rdv, pub_tile, xb, bflag);
-  else if (nb == 6) bs3_run<5>(b, y, rdv, pub_tile, xb, bflag);
-  else bs3_run<4>(b, y, rdv, pub_tile, xb, bflag);
-  double x0 = y[0], x1 = y[4];
-#pragma unroll
-  for (int t = 1; t < 4; ++t) {
-    x0 = g == t ? y[t] : x0;
-    x1 = g == t ? y[t + 4] : x1;
-  }
-  x[0] = x0;
-  x[1] = x1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4913,25 +4068,6 @@ struct LdlOut {
   int ok;
 };
 
-// One factorisation step set with the column broadcast through LDS instead of v_readlane: at step k every lane j
-// publishes its S[j][k] (column k of the trailing matrix, D_k at j = k) and lanes i > k read the column back as
-// broadcasts (ds_read_b128 pairs): ~1.5 instructions per updated entry instead of ~3.5.
-template <int CM, int K0, int K1>
-__device__ __forceinline__ void ldl_steps_lds(double (&row)[CM], int lane, bool& ok, double& rD, double* pub) {
-#pragma unroll
-  for (int k = K0; k < K1; ++k) {
-    if (lane < CM) pub[lane] = row[k];
-    KB_WAVE_SYNC();  // the other lanes' column entries: no reuse of an earlier read across this point
-    const double Dk = pub[k];
-    ok = ok && (Dk > 0.0);
-    const double rdk = recip_d(Dk);
-    rD = (lane == k) ? rdk : rD;
-    const double f = (lane > k) ? row[k] * rdk : 0.0;
-#pragma unroll
-    for (int j = k + 1; j < CM; ++j) row[j] -= f * pub[j];
-  }
-}
-
 template <int CM>
 __device__ __forceinline__ LdlOut ldl_solve_reg(const KbDev& d, const double* S, const double* bv, int C, int lane,
                                                 double* pub) {
@@ -4964,7 +4100,7 @@ __device__ __forceinline__ LdlOut ldl_solve_reg(const KbDev& d, const double* S,
   for (int j = 0; j < CM; ++j) KB_KEEP(row[j]);
   if (d.dbg_stop == 45) return LdlOut{x, 1};
 #endif
-  ldl_steps<CM, 0, CM>(row, lane, ok, rD);  // (ldl_steps_lds: same speed at CM = 24, spills at CM >= 32)
+  ldl_steps<CM, 0, CM>(row, lane, ok, rD);  // (column broadcast through LDS: same speed at CM = 24, spills at CM >= 32)
 #ifdef KB_STAMPS
   KB_KEEP(rD);
 #pragma unroll
@@ -5466,13 +4602,7 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
     const int cb0 = ctab[2][0], pub_tile = N > 1 ? cb0 >> 4 : -1;
     const bool upd = do_update && okl && !(gfu && fin[0]);
     if (tid < 64) {
-#if defined(KB_BACKSOLVE1)
-      panel_backsolve(d, S, Dfac, Xinv, rDv, C, nb, pubcol, x, pub_tile, xb, &bflag);
-#elif defined(KB_BACKSOLVE3)
-      panel_backsolve3(d, S, Dfac, Xinv, rDv, C, nb, x, pub_tile, xb, &bflag);
-#else
       panel_backsolve2(d, S, Dfac, Xinv, rDv, C, nb, pubcol, x, pub_tile, xb, &bflag);
-#endif
       KB_TS(d, 8);
       if (okl && !(gfu && fin[0])) wave0_tail(gfu ? fin[1] : cur);
     } else if ((tid >> 6) == 1 && upd) {
@@ -5808,7 +4938,7 @@ __global__ void __launch_bounds__(64 * kCovWaves) k_cov_frames(KbDev d, const do
   if (!sok) return;  // k_cov_cam (or the Schur step) failed: nothing to write
 #pragma unroll
   for (int ks = 0; ks < kCovKS; ++ks) a[ks] = (rowok && 4 * ks + kq < C) ? a[ks] : 0.0;
-  // (H_ff + D_f)^-1 = L^-T D^-1 L^-1, every index static (frame_ldl's factorisation)
+  // (H_ff + D_f)^-1 = L^-T D^-1 L^-1, every index static (frame_ldl_cols' factorisation)
   {
 #pragma unroll
     for (int i = 0; i < 6; ++i) L[i][i] += dg[i];

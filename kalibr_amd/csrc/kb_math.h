@@ -59,11 +59,6 @@ __device__ __forceinline__ void update_pose(const double* in, const double* d6, 
   out[6] = in[6] + d6[5];
 }
 
-__device__ __forceinline__ int model_nintr(int m) {
-  return (m == KB_PINHOLE_RADTAN || m == KB_PINHOLE_EQUI) ? 8 : m == KB_OMNI_RADTAN ? 9
-         : (m == KB_EUCM || m == KB_DS)                   ? 6 : 5;
-}
-
 // Equidistant: y *= thetad / r, theta = atan r (scaling 1 for r <= 1e-8).  Jd = d(y')/dy (2x2, row-major),
 // Jk = d(y')/dk (2x4, row-major), both evaluated at the undistorted y, as the reference does.
 __device__ __forceinline__ void equi(const double* k, double& x, double& y, double* Jd, double* Jk) {

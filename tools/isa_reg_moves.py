@@ -7,10 +7,10 @@ v_accvgpr_read_b32: each one a full VALU issue slot, none of them counted by the
 every k_buildp / k_build instantiation of a build unit this prints the registers and scratch the assembler reports, and
 the number of v_accvgpr_*, v_readlane / v_writelane and all instructions in the whole kernel and inside the view loop:
 the smallest loop (a label and a later branch back to it) that contains every v_mfma_f64_4x4x4 of the kernel, or every
-v_mfma_f64_16x16x4 where the kernel has no 4x4x4 (KB_SYRK16, k_build).
+v_mfma_f64_16x16x4 where the kernel has no 4x4x4 (k_build).
 
   python tools/isa_reg_moves.py kalibr_amd/csrc/kb_build_tu.hip -DKB_TU_ID=0
-  python tools/isa_reg_moves.py kalibr_amd/csrc/kb_build_tu.hip -DKB_TU_ID=0 -DKB_BUILDP_VGPR=1 --kernel 'k_buildp<7, true'
+  python tools/isa_reg_moves.py kalibr_amd/csrc/kb_build_tu.hip -DKB_TU_ID=0 -DKB_SYRK_DPP --kernel 'k_buildp<7, true'
   python tools/isa_reg_moves.py --asm saved.s
 """
 import argparse
