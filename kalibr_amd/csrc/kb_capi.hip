@@ -1600,8 +1600,7 @@ static int enqueue_marginal(kb_handle* h, const kb_marginal_options* o, int writ
   if (!rc) rc = launch_colsum(h, 0);
   h->d.host_lambda = lam_saved;
   if (rc) return rc;
-  bool stage_v0;
-  const size_t lds = sizeof(double) * (size_t)marg_lds_doubles(C, stage_v0);
+  const size_t lds = marg_lds_bytes(C);
   KB_HIP(hipFuncSetAttribute(marg_fn(C), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(marg_kernel(C), dim3(1), dim3(marg_block(C)), lds, h->stream, h->d, m, 0);
   KB_HIP(hipGetLastError());
@@ -2231,8 +2230,7 @@ static int optimize_marginal(kb_handle* h, const kb_optimizer_options* opts, con
   m.V = h->marg_buf;
   m.sv = m.V + (size_t)C * C;
   m.info = m.sv + C;
-  bool stage_v0;
-  h->lds_marg = sizeof(double) * (size_t)marg_lds_doubles(C, stage_v0);
+  h->lds_marg = marg_lds_bytes(C);
   KB_HIP(hipFuncSetAttribute(marg_fn(C), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_marg));
   // the captured passes hold the k_marg arguments: other options (or a grown problem: norm_tol) recapture them
   if (std::memcmp(&m, &h->marg, sizeof(KbMarg)) != 0) {

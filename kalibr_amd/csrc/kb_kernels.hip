@@ -419,6 +419,9 @@ struct ChainLds {
   double sR[KB_MAX_CAMS][9], st[KB_MAX_CAMS][3];  // baseline B_j
   double PR[64][12];  // pair (i, j) at i(i+1)/2 + j + 1: R (9) | t (3); C <= 111 bounds the rig to N <= 10 (55 pairs)
 };
+// k_marg's tail keeps it at the start of its dynamic LDS (marg_lds_bytes); tests/marginal_cases.py restates the size
+// (CHAIN_LDS_BYTES) for the check that k_marg's LDS fits at every width
+static_assert(sizeof(ChainLds) == 7680, "ChainLds: update CHAIN_LDS_BYTES in tests/marginal_cases.py");
 // part 1: the baselines and the pair products (threads tx < np; WAVE: one wave alone, wave-level LDS syncs)
 template <bool WAVE>
 __device__ __forceinline__ void chain_pairs(const KbDev& d, const double* base, ChainLds& L, int tx) {
@@ -2629,7 +2632,7 @@ __global__ void __launch_bounds__(256) k_camexpand(KbDev d, int gate) {
 // Warm start (mo.warm): the sweeps run on V0^T (G S G) V0 from the previous call's V0 (sorted columns, any orthogonal
 // matrix is a valid start), V = V0 J...; the successive systems of a GN loop differ little, so the start is nearly
 // diagonal and the quadratic convergence takes 2-3 sweeps instead of 8-10.  Every kMargWarmMax-th call is cold.
-// One block of marg_threads(C).  LDS: marg_lds_doubles(C) doubles (C <= kMargMaxC).
+// One block of marg_threads(C).  Dynamic LDS: marg_lds_bytes(C) (C <= kMargMaxC).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ int pk_up(int i, int j, int n) {  // packed upper index, any order
   const int a = min(i, j), b = max(i, j);
@@ -2734,6 +2737,14 @@ __host__ __device__ __forceinline__ int marg_lds_doubles(int C, bool& stage_v0) 
   stage_v0 = base + C * C <= kMargLdsStage;
   return stage_v0 ? base + C * C : base;
 }
+// k_marg's dynamic LDS in bytes: the SVD's arrays, and never less than the chains of the gated tail (marg_tail), which
+// take the start of it once the solve is done -- as a static array of their own they put C = 95, 96 and 111 past the
+// 160 KB of a CU
+__host__ __device__ __forceinline__ size_t marg_lds_bytes(int C) {
+  bool stage_v0;
+  const size_t b = sizeof(double) * (size_t)marg_lds_doubles(C, stage_v0);
+  return b > sizeof(ChainLds) ? b : sizeof(ChainLds);
+}
 
 // k_marg's block: one thread per item (marg_threads), plus wave 0 for the rotations when Omega is stored full
 __host__ __device__ __forceinline__ int marg_block(int C) {
@@ -2749,20 +2760,21 @@ __device__ __forceinline__ bool rr_is_pair(int M1, int r, int c2, int x, int y) 
   return (s >= M1 ? s - M1 : s) == c2;
 }
 
-__device__ void marg_tail(const KbDev& d, double* nbase, int sok);
+__device__ void marg_tail(const KbDev& d, double* nbase, ChainLds& L, int sok);
 
 template <bool kFull>
 __global__ void __launch_bounds__(kMargThreads) k_marg(KbDev d, KbMarg mo, int gate) {
   __shared__ double nbase[KB_MAX_CAMS * 7];  // gated: the candidate baselines (marg_tail)
   __shared__ int sok0;
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  ChainLds& chains = *reinterpret_cast<ChainLds*>(sm);  // the tail's, over the SVD's arrays once they are dead
   if (gate) {
     if (d.ctrl->done) return;
     if (!d.ctrl->do_build) {  // no new system: the camera step's tail alone, as the separate tail kernel ran it
-      marg_tail(d, nbase, d.ctrl->solve_ok);
+      marg_tail(d, nbase, chains, d.ctrl->solve_ok);
       return;
     }
   }
-  extern __shared__ __attribute__((aligned(16))) double sm[];
   KB_TSM(d, 0);
   const int C = d.C, n = C, m = C + (C & 1), h = m / 2, M1 = m - 1, tid = threadIdx.x, nth = blockDim.x;
   const int lane = tid & 63;
@@ -3299,8 +3311,8 @@ __global__ void __launch_bounds__(kMargThreads) k_marg(KbDev d, KbMarg mo, int g
   }
   KB_TSM(d, 11);
   if (gate) {  // the device loop: the camera step's statistics, design variables and chains (marg_tail)
-    __syncthreads();  // dx_c written
-    marg_tail(d, nbase, sok0 && okl);
+    __syncthreads();  // dx_c written, the last read of V and G done
+    marg_tail(d, nbase, chains, sok0 && okl);
   }
 }
 
@@ -3310,8 +3322,9 @@ __global__ void __launch_bounds__(kMargThreads) k_marg(KbDev d, KbMarg mo, int g
 // the camera design variables of the candidate slot (intrinsics additive, baselines by the pose update) and the
 // candidate's camera chains -- and the pass is marked pending for k_backsub / k_post
 // ---------------------------------------------------------------------------------------------
-// sok: the solve succeeded (ctrl->solve_ok after k_marg); every thread of the block calls it
-__device__ void marg_tail(const KbDev& d, double* nbase, int sok) {
+// sok: the solve succeeded (ctrl->solve_ok after k_marg); every thread of the block calls it.  L: LDS for the chains
+// (the start of k_marg's dynamic LDS, marg_lds_bytes), first written after the barrier below
+__device__ void marg_tail(const KbDev& d, double* nbase, ChainLds& L, int sok) {
   KbCtrl* c = d.ctrl;
   const int cur = c->cur;
   const int tid = threadIdx.x, nth = blockDim.x, C = d.C, N = d.N;
@@ -3355,7 +3368,10 @@ __device__ void marg_tail(const KbDev& d, double* nbase, int sok) {
     }
   }
   __syncthreads();
-  chain_block(d, nbase, 1 - cur, nth);  // chains of the candidate (k_backsub's cost, the next build if accepted)
+  // chains of the candidate (k_backsub's cost, the next build if accepted): chain_block on the caller's LDS
+  chain_pairs<false>(d, nbase, L, tid);
+  __syncthreads();
+  chain_write(d, L, 1 - cur, tid, nth);
 }
 
 // ---------------------------------------------------------------------------------------------

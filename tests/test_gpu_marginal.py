@@ -57,13 +57,20 @@ def test_solve_marginal_matches_oracle(capi, oracle_mod, name):
     assert np.abs(ai["sv"] - ai_o["sv"]).max() <= 1e-11 * ai_o["sv"][0]
 
 
-def test_one_view_is_rank_deficient(capi):
+def test_one_view_is_rank_deficient(capi, oracle_mod):
     p = PROBLEMS["c1_one_view"]()
     g = capi.Solver(p)
     g.set_state(p.state_init)
     g.build()
     ok, dx, info = g.solve_marginal()
     assert ok and info["rank"] < p.cam_cols and np.isfinite(dx).all()
+    # the truncated solve against the oracle; that its tolerance stands clear of the singular values on either side
+    # (so that the ranks must agree) is asserted on the CPU, test_marginal_cases.py::test_one_view_rig
+    o = oracle_mod.Oracle(p)
+    ok_o, dx_o, info_o = o.solve_marginal(o.arrow(p.state_init))
+    assert ok_o and info["rank"] == info_o["rank"]
+    assert np.abs(info["sv"] - info_o["sv"]).max() <= 1e-11 * info_o["sv"][0]
+    assert np.abs(dx - dx_o).max() <= 1e-8 * np.abs(dx_o).max()
 
 
 def _gn_marginal_loop(g, max_iterations=20, eps_x=1e-3, eps_j=1e-3):
