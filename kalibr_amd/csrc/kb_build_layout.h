@@ -4,11 +4,15 @@
 #pragma once
 #include <cstddef>
 
+#include "kb_solve_layout.h"
+
 namespace kb_blay {
 
 constexpr int kXS = 17;            // kb_kernels.hip's XS (kb_capi.hip asserts that the two agree)
 constexpr int kTargetLds = 1536;   // kb_kernels.hip's kTargetLds
-constexpr size_t kLdsLimit = 160 * 1024;
+constexpr int kBuildpMaxCams = 8;  // kb_kernels.hip's kBuildpMaxCams
+constexpr int kMaxBuildThreads = 512;  // the build kernels' launch bound
+constexpr size_t kLdsLimit = kb_slay::kLdsLimit;
 constexpr size_t kBuildpStaticLds = 4096;  // k_buildp's static LDS (control copies, tables, counters), an upper bound
 
 struct Rig {
@@ -19,13 +23,20 @@ struct Rig {
   int bpc;  // k_buildp blocks per CU
 };
 
+// k_build's waves per camera (at least 4 waves per block) and per block
+inline int nsplit(int N) { return (4 + N - 1) / N > 1 ? (4 + N - 1) / N : 1; }
+inline int build_wpb(int N) { return N * nsplit(N); }
+// a rig of N cameras fits a build block: at most 8 cameras
+inline bool cams_fit(int N) { return 64 * build_wpb(N) <= kMaxBuildThreads; }
+// kb_create's choice of the pipelined build (k_buildp: N view waves + the frame waves): one wave per camera
+inline bool pipe_default(int N) { return nsplit(N) == 1 && N <= kBuildpMaxCams; }
+
 // frames per build block for F frames
 inline int gframes(bool pipe, int bpc, int F) { return pipe ? (F + 256 * bpc - 1) / (256 * bpc) : (F + 511) / 512; }
 
 // k_buildp's frame waves
 inline int frame_waves(int C) {
-  const int nbz = (C + 16) / 16;
-  return (nbz * (nbz + 1) / 2 + 1) / 2 <= 5 ? 2 : 4;
+  return (kb_slay::ntiles(C) + 1) / 2 <= 5 ? 2 : 4;
 }
 
 // threads per build block
@@ -35,7 +46,7 @@ inline int build_threads(const Rig& r, bool pipe) { return 64 * (pipe ? r.N + fr
 // the target corners in LDS too
 inline size_t build_lds(const Rig& r, bool pipe, int gf, int* tg_out) {
   const int N = r.N, C = r.C;
-  const int CZ = 16 * ((C + 16) / 16);  // [Y | z] row stride of the Schur tiles
+  const int CZ = 16 * kb_slay::nb(C);  // [Y | z] row stride of the Schur tiles
   const int tgl = (3 * r.K <= kTargetLds ? 3 * r.K : 0) + 8 * gf;
   if (pipe) {  // k_buildp: tiles | H | chains G | view outputs | frame sums | frame-wave buffers | K | target,
                // poses | the second view-output buffer

@@ -60,8 +60,7 @@ int nintr_host(int m) {
 
 constexpr int kGraphPasses = 8;  // optimizer passes per captured multi-pass graph
 constexpr int kGnOneGraph = 64;  // kb_gn_launch: runs of up to this many GN passes are one graph (with the loop's end)
-constexpr int kXMaxRanks = 64;
-constexpr int kPolicyMarginal = 2;  // graph policy id of kb_optimize_marginal's passes (GN over the marginal solve)   // expanded partials: per-rank max|dx_f| slots in the image's aux area
+constexpr int kPolicyMarginal = 2;  // graph policy id of kb_optimize_marginal's passes (GN over the marginal solve)
 constexpr int kPolicyDogleg = 3;   // graph policy id of the dog-leg passes (kb_optimize policy 2)
 constexpr int kLocalMaxRanks = 16;  // kb_comm_init_local group size
 
@@ -163,12 +162,15 @@ struct kb_handle {
   bool gn_graph = false;
   int build_threads = 64;
   size_t lds_build = 0, lds_camexp = 0, lds_schur = 0, lds_solve = 0;
+  size_t lds_cov_cam = 0, lds_cov_frames = 0;  // kb_covariance's kernels (sized with the rest at kb_create)
+  bool cov_ok = false;                         // ... and whether they fit: kb_covariance refuses the rig otherwise
   int solve_threads = 64;
   int mb = 7, ms = 7;  // Schur-sum tiles per wave of k_build / k_schur (template bucket)
   const void* fn_build = nullptr;
   const void* fn_build_gn = nullptr;  // GN fused passes
   const void* fn_schur = nullptr;
   const void* fn_solve = nullptr;
+  const void* fn_cov_cam = nullptr;  // k_cov_cam<CM> of fn_solve's CM
   int cur = 0;  // host mirror of ctrl->cur for the per-call path
   bool uploaded = false;
   std::vector<void*> allocs;
@@ -331,6 +333,26 @@ static void set_frame_counts(kb_handle* h) {
 using kb_blay::kBuildpStaticLds;
 static_assert(kb_blay::kXS == XS && kb_blay::kTargetLds == kTargetLds, "kb_build_layout.h: kernel constants");
 static_assert(kb_blay::kViewtabStride == kVtStride && kb_blay::kViewtabRec <= kVtStride, "kb_build_layout.h: view table");
+static_assert(kb_blay::kBuildpMaxCams == kBuildpMaxCams, "kb_build_layout.h: k_buildp's cameras");
+
+// k_solve<CM> and k_cov_cam<CM> of one camera-block width: both by kb_solve_layout.h's solve_cm
+struct CmKernels {
+  const void *solve, *cov_cam;
+};
+template <int CM>
+static CmKernels cm_pair() {
+  return {(const void*)k_solve<CM>, (const void*)k_cov_cam<CM>};
+}
+static CmKernels cm_kernels(int C) {
+  switch (solve_cm(C)) {
+    case 16: return cm_pair<16>();
+    case 24: return cm_pair<24>();
+    case 32: return cm_pair<32>();
+    case 48: return cm_pair<48>();
+    case 64: return cm_pair<64>();
+    default: return cm_pair<0>();
+  }
+}
 static kb_blay::Rig layout_rig(const kb_handle* h) { return {h->N, h->C, h->K, h->d.wpb, h->bpc}; }
 
 // k_buildp's per-view table (kb_build_layout.h) rides behind the rest where it fits at the handle's frame count,
@@ -471,9 +493,8 @@ static int relayout(kb_handle* h) {
 // KB_ROBUST_BUILD_PIPE mode the weighted k_buildp pair (general pass | fused GN pass).
 static void set_build_kernels(kb_handle* h) {
   const KbDev& d = h->d;
-  const int nbz = (h->C + 16) / 16, ntiles = nbz * (nbz + 1) / 2;
-  const int tb = (ntiles + d.wpb - 1) / d.wpb;
-  h->mb = h->build_pipe ? ((ntiles + 1) / 2 <= 5 ? 5 : 7) : tb <= 1 ? 1 : tb <= 4 ? 4 : 7;
+  const int nt = ntiles(h->C), tb = (nt + d.wpb - 1) / d.wpb;
+  h->mb = h->build_pipe ? ((nt + 1) / 2 <= 5 ? 5 : 7) : tb <= 1 ? 1 : tb <= 4 ? 4 : 7;
   unsigned mm = 0;
   for (int i = 0; i < h->N; ++i) mm |= 1u << d.model[i];
   const bool vt = h->build_pipe && h->viewtab;  // the instantiations that carry the per-view table (build_lds decides)
@@ -579,7 +600,8 @@ kb_handle* kb_create(const kb_layout* L) {
     c += 6;
   }
   h->C = c;
-  if (h->C > 111) {  // [Y | z] Schur tiles: ceil((C + 1) / 16) <= 7 (7 tiles per wave of 4)
+  static_assert(kMaxC == 111, "the refusal below names the limit");
+  if (h->C > kMaxC) {  // [Y | z] Schur tiles: ceil((C + 1) / 16) <= 7 (7 tiles per wave of 4)
     fail("kb_create: camera block C > 111 not supported");
     delete h;
     return nullptr;
@@ -588,17 +610,17 @@ kb_handle* kb_create(const kb_layout* L) {
   d.C = h->C;
   d.off_base = h->N * KB_MAX_INTR;
   d.off_frame = h->N * KB_MAX_INTR + 7 * (h->N - 1);
-  d.nsplit = std::max(1, (4 + h->N - 1) / h->N);  // >= 4 waves per build block
-  d.wpb = h->N * d.nsplit;
+  d.nsplit = kb_blay::nsplit(h->N);  // >= 4 waves per build block
+  d.wpb = kb_blay::build_wpb(h->N);
   h->WPB = d.wpb;
   // one wave per camera and at most kBuildpMaxCams cameras: the pipelined build (N view waves + 2 frame waves);
   // KB_BUILD_PIPE=0 keeps k_build for comparison
-  h->build_pipe = d.nsplit == 1 && h->N <= kBuildpMaxCams;
+  h->build_pipe = kb_blay::pipe_default(h->N);
   if (const char* e = std::getenv("KB_BUILD_PIPE")) h->build_pipe = h->build_pipe && std::atoi(e) != 0;
   h->build_pipe0 = h->build_pipe;
   d.rb_l[0] = d.rb_l[2] = 1.0;  // no invR: the identity factor
-  const int nbz0 = (h->C + 16) / 16, nf = (nbz0 * (nbz0 + 1) / 2 + 1) / 2 <= 5 ? 2 : 4;  // k_buildp frame waves
-  h->build_threads = 64 * (h->build_pipe ? h->N + nf : d.wpb);
+  const int nf = kb_blay::frame_waves(h->C);  // k_buildp frame waves
+  h->build_threads = kb_blay::build_threads(layout_rig(h), h->build_pipe);
   if (h->build_pipe) {
     // all blocks resident at once: one block per CU (two for rigs whose block fits twice: 12 waves per CU at the
     // kernel's <= 168 VGPRs, half the LDS), each running its frames through the pipeline
@@ -619,7 +641,7 @@ kb_handle* kb_create(const kb_layout* L) {
   d.Wtot = d.Wp + 1;  // + per-rank max|dx_f| column(s); kb_comm_init widens it to nranks
   d.nranks = 1;
   d.rank = 0;
-  if (64 * d.wpb > 512) {
+  if (!kb_blay::cams_fit(h->N)) {
     fail("kb_create: camera block / rig too large for the build kernel");
     delete h;
     return nullptr;
@@ -662,9 +684,9 @@ kb_handle* kb_create(const kb_layout* L) {
   rc |= h->alloc(&d.red_local, 8);
   d.red = d.red_local;
   rc |= h->alloc(&d.ctrl, 1);
-  if (h->C > 64) {  // k_solve's staged camera block (k_colimg / k_colsumx), sized as in the LDS budget below
-    const int nb = (h->C + 16) / 16;  // rows 0 .. C: the right-hand side is appended as row C
-    rc |= h->alloc(&d.simg, (size_t)kTileSz * nb * (nb + 1) / 2 + 16 * nb + 2 + kXMaxRanks);
+  if (!solve_cm(h->C)) {  // k_solve<0>'s staged camera block (k_colimg / k_colsumx)
+    d.img_n = img_n(h->C);
+    rc |= h->alloc(&d.simg, (size_t)d.img_n);
   }
   std::vector<int32_t> colinfo(h->C), tri(h->C * (h->C + 1) / 2);
   for (int i = 0; i < h->N; ++i)
@@ -688,54 +710,42 @@ kb_handle* kb_create(const kb_layout* L) {
   hipMemcpyAsync(tr, tri.data(), tri.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
   hipMemcpyAsync(tgt, L->target_points, 3 * sizeof(double) * h->K, hipMemcpyHostToDevice, h->stream);
   {
-    const int N = h->N, C = h->C, WPB = d.wpb;
-    const int CZ = 16 * ((C + 16) / 16);  // [Y | z] row stride of the Schur tiles
-    (void)WPB;
+    // the reduced-system kernels' instances, threads and dynamic LDS: kb_solve_layout.h
+    const int N = h->N, C = h->C;
     h->lds_build = build_lds(h);
-    h->lds_camexp = sizeof(double) * (N * 256 + N * N * 36);
-    h->lds_schur = sizeof(double) * 16 * CZ;
-    if (C <= 64) {
-      h->lds_solve = sizeof(double) * (C * (C + 1) / 2 + 2 * C + 1 + N * 256 + 2 * N * N * 36) + sizeof(int) * C;
-    } else {  // the k_colimg image (complete system: 16 x 16 lower tiles, b as row C | g_c) + the factored diagonal
-      // tiles and their inverses + 1/D
-      const int nb = (C + 16) / 16, n16 = 16 * nb;
-      // tiles | aux: g_c (n16, non-PD count at C) | cost | max|dx_f| per rank (expanded partials) | pad
-      d.img_n = kTileSz * nb * (nb + 1) / 2 + n16 + 2 + kXMaxRanks;
-      h->lds_solve = sizeof(double) * (d.img_n + 2 + 2 * nb * kTileSz + n16) + sizeof(int) * C;
-      h->lds_colimg = sizeof(double) * (N * 256 + 2 * N * N * 36) + sizeof(int) * C;
-    }
-    h->solve_threads = C <= 64 ? 256 : 512;
+    h->lds_camexp = lds_camexp(N);
+    h->lds_schur = lds_schur(C);
+    h->lds_solve = lds_solve(N, C);
+    h->lds_colimg = lds_colimg(N, C);
+    h->lds_cov_cam = lds_cov_cam(N, C);
+    h->lds_cov_frames = lds_cov_frames(C);
+    h->cov_ok = cov_fits(N, C);
+    h->solve_threads = solve_threads(C);
     // expanded partials for the GN fused loop: k_buildp expands its own camera sums in the LDS its view tiles free
     // (Hs [N][256] | T [N(N-1)/2][36] | H_cc, g_c [W] within the Xw + Hw regions); KB_XEXP=0 keeps k_colimg
     h->xexp = C > 64 && h->build_pipe && N * 256 + 18 * N * (N - 1) + h->W <= N * 64 * XS + N * 256;
     if (const char* e = std::getenv("KB_XEXP")) h->xexp = h->xexp && std::atoi(e) != 0;
-    h->fn_solve = C <= 16   ? (const void*)k_solve<16>
-                  : C <= 24 ? (const void*)k_solve<24>
-                  : C <= 32 ? (const void*)k_solve<32>
-                  : C <= 48 ? (const void*)k_solve<48>
-                  : C <= 64 ? (const void*)k_solve<64>
-                            : (const void*)k_solve<0>;
-    if (h->lds_build + (h->build_pipe ? kBuildpStaticLds : 0) > 160 * 1024 || h->lds_solve > 160 * 1024 ||
-        h->lds_camexp > 160 * 1024) {
+    h->fn_solve = cm_kernels(C).solve;
+    h->fn_cov_cam = cm_kernels(C).cov_cam;
+    if (h->lds_build + (h->build_pipe ? kBuildpStaticLds : 0) > kb_blay::kLdsLimit || !solve_fits(N, C)) {
       fail("kb_create: LDS budget exceeded for this rig");
       kb_destroy(h);
       return nullptr;
     }
   }
-  {
-    // Schur-sum tiles per wave (template bucket): ceil(lower tiles of [Y|z]^T [Y|z] / waves)
-    const int nbz = (h->C + 16) / 16, ntiles = nbz * (nbz + 1) / 2;
-    const int ts = (ntiles + 3) / 4;
-    h->ms = ts <= 1 ? 1 : ts <= 4 ? 4 : 7;
-    set_build_kernels(h);
-    h->fn_schur = h->ms == 1 ? (const void*)k_schur<1> : h->ms == 4 ? (const void*)k_schur<4> : (const void*)k_schur<7>;
-  }
+  h->ms = schur_ms(h->C);  // Schur-sum tiles per wave (template bucket)
+  set_build_kernels(h);
+  h->fn_schur = h->ms == 1 ? (const void*)k_schur<1> : h->ms == 4 ? (const void*)k_schur<4> : (const void*)k_schur<7>;
   hipFuncSetAttribute(h->fn_build, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_build);
   hipFuncSetAttribute(h->fn_build_gn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_build);
   hipFuncSetAttribute((const void*)k_camexpand, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_camexp);
   hipFuncSetAttribute(h->fn_schur, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_schur);
   hipFuncSetAttribute(h->fn_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_solve);
   hipFuncSetAttribute((const void*)k_colimg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_colimg);
+  if (h->cov_ok) {  // kb_covariance's two kernels: sized by N and C alone, so once per handle
+    hipFuncSetAttribute(h->fn_cov_cam, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_cov_cam);
+    hipFuncSetAttribute((const void*)k_cov_frames, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_cov_frames);
+  }
   if (hipStreamSynchronize(h->stream) != hipSuccess) {
     fail("kb_create: stream sync failed");
     kb_destroy(h);
@@ -1554,7 +1564,8 @@ int kb_revert(kb_handle* h) {
 }
 
 // ---------------------------------------------------------------- marginal SVD solver (calibration::LinearSolver)
-// the k_marg instance for C: full-storage Omega while it fits in LDS, packed upper beyond
+// the k_marg instance for C: full-storage Omega while it fits in LDS, packed upper beyond.  Every width a handle admits
+// is within k_marg's array capacity (kMargMaxC) and its LDS (marg_fits): kb_solve_layout.h asserts both
 using MargKernel = void (*)(KbDev, KbMarg, int);
 static MargKernel marg_kernel(int C) { return marg_full(C) ? k_marg<true> : k_marg<false>; }
 static const void* marg_fn(int C) { return (const void*)marg_kernel(C); }
@@ -1579,7 +1590,6 @@ static void marg_info(const double* inf, kb_marginal_info* info) {
 // caller syncs)
 static int enqueue_marginal(kb_handle* h, const kb_marginal_options* o, int write_dx, double* inf, double* sv_out,
                             double* V_out) {
-  if (h->C > kMargMaxC) return fail("marginal solver: camera block C > 112 is not supported");
   if (sharded(h)) return fail("marginal solver: not available on a sharded handle");
   const int C = h->C;
   const size_t mstride = (size_t)C * C + C + 8;
@@ -1726,16 +1736,8 @@ int kb_rhs_jtj_rhs(kb_handle* h, double* out) {
 
 // Blocks of (J^T J + D)^-1 of the per-call system (the Schur form of BlockCholeskyLinearSystemSolver::
 // computeCovarianceBlocks): the Schur step and column sums of kb_solve, then k_cov_cam (S -> Sigma_cc, one launch)
-// and k_cov_frames (Sigma_fc, Sigma_ff).  Always the direct factorisation, whatever kb_set_solver chose.
-static const void* cov_cam_fn(int C) {
-  return C <= 16   ? (const void*)k_cov_cam<16>
-         : C <= 24 ? (const void*)k_cov_cam<24>
-         : C <= 32 ? (const void*)k_cov_cam<32>
-         : C <= 48 ? (const void*)k_cov_cam<48>
-         : C <= 64 ? (const void*)k_cov_cam<64>
-                   : (const void*)k_cov_cam<0>;
-}
-
+// and k_cov_frames (Sigma_fc, Sigma_ff).  Always the direct factorisation, whatever kb_set_solver chose.  kb_create
+// picked k_cov_cam's instance and sized both kernels' LDS (kb_solve_layout.h).
 int kb_covariance(kb_handle* h, double* Pcc, double* Pff, double* Pfc, int* ok) {
   if (!h || !ok) return fail("kb_covariance: null");
   if (!h->uploaded) return fail("kb_covariance: no observations");
@@ -1743,7 +1745,7 @@ int kb_covariance(kb_handle* h, double* Pcc, double* Pff, double* Pfc, int* ok) 
   if (!h->sys_valid) return fail("kb_covariance: no intact system (call kb_build first; the optimizer loops do "
                                  "not leave the per-call blocks)");
   const int C = h->C, F = h->F;
-  if (C > kCovMaxC) return fail("kb_covariance: camera block C > 112 is not supported");
+  if (!h->cov_ok) return fail("kb_covariance: LDS budget exceeded for this rig");
   KB_HIP(hipSetDevice(h->device));
   unprepare(h);
   if (!h->cov_cc && h->alloc(&h->cov_cc, (size_t)C * C)) return fail("kb_covariance: allocation failed");
@@ -1764,27 +1766,15 @@ int kb_covariance(kb_handle* h, double* Pcc, double* Pff, double* Pfc, int* ok) 
   } cs(h);
   if (launch_schur(h, 0)) return -1;
   if (launch_colsum(h, 0)) return -1;
-  const void* fn = cov_cam_fn(C);
-  const int nct = (C + 15) / 16;
-  const size_t lds_frames = sizeof(double) * ((size_t)C * C + (size_t)kCovWaves * 16 * (16 * nct + 1));
-  // k_cov_cam: the solve's LDS layout + one packed triangle (L or its inverse): behind the layout (C <= 64), or from
-  // the diagonal tiles' inverses on (C > 64: tiles | aux | factored diagonal tiles come first, as in solve_body)
-  const int nb16 = (C + 16) / 16;
-  const int eoff = C <= 64 ? (int)((h->lds_solve + 15) / 16) * 2
-                           : kTileSz * nb16 * (nb16 + 1) / 2 + ((16 * nb16 + 3) & ~1) + nb16 * kTileSz;
-  const size_t lds_cam = std::max(h->lds_solve, sizeof(double) * ((size_t)eoff + (size_t)C * (C + 1) / 2));
-  if (lds_cam > 160 * 1024 || lds_frames > 160 * 1024) return fail("kb_covariance: LDS budget exceeded for this rig");
-  KB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cam));
-  KB_HIP(hipFuncSetAttribute((const void*)k_cov_frames, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_frames));
   KbDev d = h->d;
   double* cc = h->cov_cc;
-  int eo = eoff;
+  int eo = cov_eoff(h->N, C);  // k_cov_cam's second packed triangle, behind the solve's LDS layout
   void* args[] = {(void*)&d, (void*)&cc, (void*)&eo};
-  KB_HIP(hipLaunchKernel(fn, dim3(1), dim3(h->solve_threads), args, lds_cam, h->stream));
+  KB_HIP(hipLaunchKernel(h->fn_cov_cam, dim3(1), dim3(h->solve_threads), args, h->lds_cov_cam, h->stream));
   KB_HIP(hipGetLastError());
   if (Pff || Pfc) {
-    hipLaunchKernelGGL(k_cov_frames, dim3((F + kCovFrames - 1) / kCovFrames), dim3(64 * kCovWaves), lds_frames, h->stream,
-                       d, (const double*)h->cov_cc, h->cov_ff, Pfc ? h->cov_fc : (double*)nullptr);
+    hipLaunchKernelGGL(k_cov_frames, dim3((F + kCovFrames - 1) / kCovFrames), dim3(64 * kCovWaves), h->lds_cov_frames,
+                       h->stream, d, (const double*)h->cov_cc, h->cov_ff, Pfc ? h->cov_fc : (double*)nullptr);
     KB_HIP(hipGetLastError());
   }
   // the outputs are written only when the factorisation succeeded: Pcc and Pff (0.7 MB at configs[3]) are staged on
@@ -2215,7 +2205,6 @@ static int optimize_marginal(kb_handle* h, const kb_optimizer_options* opts, con
   if (!h->uploaded) return fail("kb_optimize_marginal: no observations");
   KB_REFUSE_WEIGHTED(h, "kb_optimize_marginal");
   if (opts->policy != 1) return fail("kb_optimize_marginal: the IncrementalEstimator's policy is Gauss-Newton (1)");
-  if (h->C > kMargMaxC) return fail("kb_optimize_marginal: camera block C > 112 is not supported");
   if (sharded(h)) return fail("kb_optimize_marginal: not available on a sharded handle");
   KB_HIP(hipSetDevice(h->device));
   const int C = h->C;

@@ -17,8 +17,13 @@
 #include <stdint.h>
 
 #include "kb_math.h"
+#include "kb_solve_layout.h"
 
 namespace kb {
+
+// the reduced-system launch layout: limits, selectors, LDS maps and k_marg's sizes (kTS, kTileSz, kXMaxRanks, kCovWaves,
+// kCovMaxC, kMargMaxC, kMargThreads, kMargLdsStage, nb, solve_map, marg_threads, marg_block, ...)
+using namespace kb_slay;
 
 struct KbCtrl {
   int cur, done, do_build, solve_ok, first, prev_failed, lin_fail;
@@ -43,21 +48,11 @@ constexpr int kXarFlagDoubles = 64;   // flag area of an exchange region (kXarBl
 constexpr unsigned long long kXarTimeoutTicks = 1000000000ull;  // default wait bound: 10 s of s_memrealtime (100 MHz)
 
 // k_marg (marginal truncated-SVD camera solve, aslam_incremental_calibration LinearSolver)
-constexpr int kMargThreads = 1024;
-constexpr int kCovMaxC = 112;          // kb_covariance: Sigma_cc [C][C] + four waves' product tiles in LDS <= 160 KB
-constexpr int kMargMaxC = 112;         // packed Omega + V in LDS: C(C+1)/2 + C^2 + 2C doubles <= 160 KB
 constexpr int kMargMaxSweeps = 40;
 constexpr double kMargJacobiTol = 1.1102230246251565e-16;  // skip |a_pq| <= 2^-53 sqrt|a_pp a_qq|
 constexpr int kMargItems = 8;    // k_marg items (2x2 blocks, rows of V) per thread at C <= kMargMaxC
 constexpr int kMargWarmMax = 32;     // consecutive warm starts before a cold (identity) start bounds V's orthogonality drift
 constexpr int kMargFullMaxC = 96;   // largest C whose full-storage Omega (padded to even) + V fit kMargLdsStage
-constexpr int kMargLdsStage = 19000;  // dynamic LDS doubles up to which V0 is staged in LDS too (static ~9 KB beside)
-// block size of k_marg: one thread per 2x2 block of pairs and per (row of V, pair), whole waves
-__host__ __device__ inline int marg_threads(int C) {
-  const int h = (C + (C & 1)) / 2, items = h * (h + 1) / 2 + C * h;
-  const int t = (items + 63) / 64 * 64;
-  return t < kMargThreads ? t : kMargThreads;
-}
 struct KbMarg {
   int scaling;      // LinearSolverOptions::columnScaling
   int write_dx;     // 1: solve (dx_c into d.dx); 0: analyzeMarginal (SVD only)

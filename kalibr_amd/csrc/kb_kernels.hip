@@ -71,9 +71,7 @@ __device__ __forceinline__ double readlane_d(double v, int lane) {
 constexpr int XS = 17;       // LDS row stride (doubles) of the 64 x 16 Jacobian-row tile
 constexpr int kTargetLds = 1536;  // target corners staged in k_build's LDS when 3 * n_target <= this
 // the camera block of the C > 64 solve in LDS (and in its global image): lower 16 x 16 tiles, tile (it, jt) at
-// (it(it+1)/2 + jt) * kTileSz, row stride kTS (see ldl_panels)
-constexpr int kTS = 17;             // tile row stride (doubles): 16 + 1 keeps row-parallel LDS accesses conflict-free
-constexpr int kTileSz = 16 * kTS;
+// (it(it+1)/2 + jt) * kTileSz, row stride kTS (kb_solve_layout.h; see ldl_panels)
 __device__ __forceinline__ int tile_base(int it, int jt) { return (it * (it + 1) / 2 + jt) * kTileSz; }
 __device__ __forceinline__ int tidx(int i, int j) { return tile_base(i >> 4, j >> 4) + (i & 15) * kTS + (j & 15); }
 
@@ -419,9 +417,9 @@ struct ChainLds {
   double sR[KB_MAX_CAMS][9], st[KB_MAX_CAMS][3];  // baseline B_j
   double PR[64][12];  // pair (i, j) at i(i+1)/2 + j + 1: R (9) | t (3); C <= 111 bounds the rig to N <= 10 (55 pairs)
 };
-// k_marg's tail keeps it at the start of its dynamic LDS (marg_lds_bytes); tests/marginal_cases.py restates the size
-// (CHAIN_LDS_BYTES) for the check that k_marg's LDS fits at every width
-static_assert(sizeof(ChainLds) == 7680, "ChainLds: update CHAIN_LDS_BYTES in tests/marginal_cases.py");
+// k_marg's tail keeps it at the start of its dynamic LDS (marg_lds_bytes, kb_solve_layout.h, which carries the size);
+// tests/marginal_cases.py restates it (CHAIN_LDS_BYTES) for the check that k_marg's LDS fits at every width
+static_assert(sizeof(ChainLds) == kChainLdsBytes, "ChainLds: update kChainLdsBytes and tests/marginal_cases.py");
 // part 1: the baselines and the pair products (threads tx < np; WAVE: one wave alone, wave-level LDS syncs)
 template <bool WAVE>
 __device__ __forceinline__ void chain_pairs(const KbDev& d, const double* base, ChainLds& L, int tx) {
@@ -820,7 +818,7 @@ __global__ void __launch_bounds__(512) k_build(KbDev d, int gate, int fuse) {
   double* dH = Pv + N * 36;          // [N][36]  G^T H_dd G
   double* dg = dH + N * 36;          // [N][8]   G^T g_d
   double* Fh = dg + N * 8;           // frame H_ff [36]
-  const int nbz = (C + 16) >> 4, CZ = 16 * nbz;
+  const int nbz = KB_SLAY_NB(C), CZ = 16 * nbz;
   double* P = Fh + 36;               // [8][CZ]: [H_fc | g_f] of the current frame, zero-padded
   double* Q = P + 8 * CZ;            // [8][CZ]: [A | b] (frame_gj), zero-padded
   double* Kl = Q + 8 * CZ;           // [N(N-1)/2][36] K_{i,j}, j < i, at (i(i-1)/2 + j)
@@ -1309,7 +1307,7 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
   const int N = d.N, C = d.C, NW = N + NF, NP = N * (N - 1) / 2;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, nth = blockDim.x;
   const int tid = threadIdx.x;
-  const int nbz = (C + 16) >> 4, CZ = 16 * nbz;
+  const int nbz = KB_SLAY_NB(C), CZ = 16 * nbz;
   const int VBS = 44 * N + 6 * CZ, FBS = 6 * CZ;
   double* Xw = sm + wave * 64 * XS;     // [N][64][XS] view waves' Jacobian-row tiles (P_v after the SYRK)
   double* PvL = sm + N * 64 * XS;       // [2][N][128] each view's P_v[:, d] (MFMA A-operand layout), by frame parity
@@ -2197,7 +2195,7 @@ __global__ void __launch_bounds__(256) k_schur(KbDev d, int gate) {
   if (gate && (c->done || c->do_build)) return;  // rebuild passes ran it fused in k_build
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int C = d.C, W = d.W, N = d.N;
-  const int nbz = (C + 16) >> 4, CZ = 16 * nbz;
+  const int nbz = KB_SLAY_NB(C), CZ = 16 * nbz;
   double* P = sm;           // [8][CZ]: [H_fc | g_f], zero-padded
   double* Q = P + 8 * CZ;   // [8][CZ]: [A | b], zero-padded
   __shared__ int okl;
@@ -2344,7 +2342,7 @@ __global__ void __launch_bounds__(64 * kColsum1Waves) k_colsumx(KbDev d, int gat
   KbCtrl* c = d.ctrl;
   __shared__ double part[kColsum1Waves][64];
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int N = d.N, C = d.C, nb = (C + 16) >> 4, n16 = 16 * nb;
+  const int N = d.N, C = d.C, nb = KB_SLAY_NB(C), n16 = 16 * nb;  // img_n16(C)
   const int x = blockIdx.x * 64 + l;
   const int nx = (C + 1) + (d.Wtot - N * 136);
   const int e = x <= C ? x : x - (C + 1) + N * 136;
@@ -2379,7 +2377,7 @@ __global__ void __launch_bounds__(64 * kColsum1Waves) k_colsumx(KbDev d, int gat
     t += part[q][l];
     m = fmax(m, part[q][l]);
   }
-  const int ntz = kTileSz * nb * (nb + 1) / 2, aux = ntz;
+  const int aux = KB_SLAY_NTZ(nb);  // img_ntz(C): the aux area behind the tiles
   const int Wt = C * (C + 1) / 2, o = N * 136;
   double* img = d.ximg;
   const bool sys = d.xar != 0;
@@ -2725,32 +2723,7 @@ __device__ __forceinline__ bool marg_rot(double app, double aqq, double apq, dou
   return big;
 }
 
-// LDS of k_marg in doubles.  Full storage (kFull: both triangles of Omega, C padded to even m, V [C][m]) while it fits,
-// else packed upper Omega and V [C][C]; then G, b_s, and V0 (the warm start) when it fits beside them
-__host__ __device__ __forceinline__ bool marg_full(int C) {
-  const int m = C + (C & 1);
-  return m * m + C * m + 2 * C <= kMargLdsStage;
-}
-__host__ __device__ __forceinline__ int marg_lds_doubles(int C, bool& stage_v0) {
-  const int m = C + (C & 1);
-  const int base = marg_full(C) ? m * m + C * m + 2 * C : C * (C + 1) / 2 + C * C + 2 * C;
-  stage_v0 = base + C * C <= kMargLdsStage;
-  return stage_v0 ? base + C * C : base;
-}
-// k_marg's dynamic LDS in bytes: the SVD's arrays, and never less than the chains of the gated tail (marg_tail), which
-// take the start of it once the solve is done -- as a static array of their own they put C = 95, 96 and 111 past the
-// 160 KB of a CU
-__host__ __device__ __forceinline__ size_t marg_lds_bytes(int C) {
-  bool stage_v0;
-  const size_t b = sizeof(double) * (size_t)marg_lds_doubles(C, stage_v0);
-  return b > sizeof(ChainLds) ? b : sizeof(ChainLds);
-}
-
-// k_marg's block: one thread per item (marg_threads), plus wave 0 for the rotations when Omega is stored full
-__host__ __device__ __forceinline__ int marg_block(int C) {
-  const int t = marg_threads(C) + (marg_full(C) ? 64 : 0);
-  return t < kMargThreads ? t : kMargThreads;
-}
+// k_marg's LDS (marg_full, marg_lds_doubles, marg_lds_bytes) and block (marg_block): kb_solve_layout.h
 
 // round r's partner test of an entry (x, y), x != y (round-robin: {r, M1} and pairs with x + y = 2r mod M1)
 __device__ __forceinline__ bool rr_is_pair(int M1, int r, int c2, int x, int y) {
@@ -3870,9 +3843,9 @@ __global__ void __launch_bounds__(kColimgThreads) k_colimg(KbDev d, const double
   const bool stamp_block = blockIdx.x == d.Wtot / (int)blockDim.x;  // diagnostic timeline: the first image block
   if (stamp_block) KB_TS(d, 50);
   const int N = d.N, C = d.C, Wt = d.W - d.C;
-  const int nb = (C + 16) >> 4, ntz = kTileSz * nb * (nb + 1) / 2;  // + the b row (row C)
+  const int nb = KB_SLAY_NB(C), ntz = KB_SLAY_NTZ(nb);  // img_ntz(C): the tiles, with the b row (row C)
   const int q0 = blockIdx.x * blockDim.x;
-  const bool img_block = q0 + nth > d.Wtot && q0 < d.Wtot + ntz + 16 * nb + 2;  // block-uniform
+  const bool img_block = q0 + nth > d.Wtot && q0 < d.Wtot + ntz + 16 * nb + 2;  // + img_n16(C) + 2; block-uniform
   // ---- this thread's output: which column sum it needs (src) and what it is
   // kind: 0 none / zero, 1 finished column sum (out), 2 camera entry (i, j), 3 b entry j, 4 identity, 5 g_c k,
   //       6 non-PD count
@@ -4313,21 +4286,10 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int N = d.N, C = d.C, W = d.W, tid = threadIdx.x;
   const int Cp = C * (C + 1) / 2;
-  const int nb = (C + 16) >> 4, n16 = 16 * nb;  // CM == 0: 16 x 16 tiles, rows 0 .. C (b appended as row C)
-  // CM > 0: S column-major packed lower [Cp] | bv [C + 1] (slot C: non-PD frame-block count) | gl [C] | Hs [N][256] |
-  //   T, K [N][N][36] | ci [C]
-  // CM == 0: the k_colimg image [S lower tiles, complete (b as row C) | gl = g_c (n16 + 2 slots, slot C: non-PD
-  //   frame-block count)] | Dfac | Xinv | 1/D
-  double* S = sm;
-  double* bv = S + (CM > 0 ? Cp : kTileSz * nb * (nb + 1) / 2);
-  double* Hs = CM > 0 ? bv + 2 * C + 1 : bv;
-  double* gl = CM > 0 ? bv + C + 1 : bv;
-  double* T = CM > 0 ? Hs + N * 256 : bv;
-  double* K = T + N * N * 36;        // CM > 0: [N][N][36]
-  double* Dfac = CM > 0 ? K + N * N * 36 : bv + ((n16 + 2 + 1) & ~1);  // CM == 0: [nb][kTileSz] factored diagonal tiles
-  double* Xinv = Dfac + (CM > 0 ? 0 : nb * kTileSz);  // CM == 0: [nb][kTileSz] their unit-lower inverses
-  double* rDv = Xinv + (CM > 0 ? 0 : nb * kTileSz);   // CM == 0: [n16] 1/D
-  int* ci = (int*)(rDv + (CM > 0 ? 0 : n16));      // [C]
+  const int nb = KB_SLAY_NB(C), n16 = 16 * nb;  // CM == 0: 16 x 16 tiles, rows 0 .. C (b appended as row C)
+  // the packed layout (CM > 0) or the k_colimg image and the factored diagonal tiles behind it: kb_solve_layout.h
+  KB_SLAY_SOLVE_MAP(double*, sm, CM > 0, N, C)  // S, bv, gl, Hs, T, K, Dfac, Xinv, rDv
+  int* ci = (int*)cip;                           // [C]
   __shared__ int okl;
   __shared__ double nbase[KB_MAX_CAMS * 7];  // candidate baselines
   __shared__ int ctab[3][KB_MAX_CAMS];       // per camera: #intrinsics | first intrinsic column | baseline column
@@ -4760,17 +4722,10 @@ __global__ void __launch_bounds__(CM == 0 ? 512 : 256) k_cov_cam(KbDev d, double
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int N = d.N, C = d.C, tid = threadIdx.x, nth = blockDim.x;
   const int Cp = C * (C + 1) / 2;
-  const int nb = (C + 16) >> 4, n16 = 16 * nb;
-  // the LDS layout of solve_body<CM>
-  double* S = sm;
-  double* bv = S + (CM > 0 ? Cp : kTileSz * nb * (nb + 1) / 2);
-  double* Hs = CM > 0 ? bv + 2 * C + 1 : bv;
-  double* T = CM > 0 ? Hs + N * 256 : bv;
-  double* K = T + N * N * 36;
-  double* Dfac = CM > 0 ? K + N * N * 36 : bv + ((n16 + 2 + 1) & ~1);
-  double* Xinv = Dfac + (CM > 0 ? 0 : nb * kTileSz);
-  double* rDv = Xinv + (CM > 0 ? 0 : nb * kTileSz);
-  int* ci = (int*)(rDv + (CM > 0 ? 0 : n16));
+  const int nb = KB_SLAY_NB(C);
+  // the LDS layout of solve_body<CM> (kb_solve_layout.h); E = sm + eoff lies behind it (cov_eoff)
+  KB_SLAY_SOLVE_MAP_NO_GL(double*, sm, CM > 0, N, C)  // S, bv, Hs, T, K, Dfac, Xinv, rDv
+  int* ci = (int*)cip;
   __shared__ int okl;
   __shared__ int ctab[3][KB_MAX_CAMS];
   __shared__ double rdl[CM > 0 ? CM : kCovMaxC];  // 1 / D
@@ -4894,14 +4849,13 @@ __global__ void __launch_bounds__(CM == 0 ? 512 : 256) k_cov_cam(KbDev d, double
 // T = A Sigma_cc is 28 k-steps x 7 column tiles at C = 112; T goes through a wave-private LDS tile (row = operand
 // row) and T A^T takes the same A registers as its B operand.  The 6 x 6 inverse is an in-register LDL^T with the
 // diagonal frame_gj uses.  Every sum has a fixed order.
-constexpr int kCovWaves = 4, kCovFrames = 2 * kCovWaves;
-constexpr int kCovKS = (kCovMaxC + 3) / 4, kCovCT = (kCovMaxC + 15) / 16;
+constexpr int kCovKS = cov_frames(kCovMaxC).nks, kCovCT = cov_frames(kCovMaxC).nct;
 __global__ void __launch_bounds__(64 * kCovWaves) k_cov_frames(KbDev d, const double* Pcc, double* Pff, double* Pfc) {
   KB_MFMA_AGPR();
   extern __shared__ __attribute__((aligned(16))) double sm[];
   __shared__ double hinv[kCovWaves][2][36];
   const int C = d.C, F = d.F, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nct = (C + 15) >> 4, nks = (C + 3) >> 2, LDT = 16 * nct + 1;
+  const int nct = cov_frames(C).nct, nks = cov_frames(C).nks, LDT = 16 * nct + 1;
   double* Sg = sm;                                   // [C][C] Sigma_cc
   double* Tw = sm + C * C + wave * 16 * LDT;          // [16][LDT] this wave's T, then [16][17] T A^T
   const int f0 = blockIdx.x * kCovFrames + 2 * wave;

@@ -4,12 +4,13 @@ the solve: shared by
 test_marginal_cases.py (the preconditions, from synth, the oracle and numpy alone) and test_gpu_marginal_shapes.py (the
 device against both references).  No GPU and no HIP import here.
 
-k_marg selects by C alone (kb_kernels.hip marg_full / marg_lds_doubles, kb_device.h kMargLdsStage = 19000 doubles):
+k_marg selects by C alone (kb_solve_layout.h marg_full / marg_lds_doubles, kMargLdsStage = 19000 doubles;
+test_solve_layout.py compares the header's figures with the restatements below at every width):
   full     both triangles of Omega in LDS, C padded to an even m (an odd C has a dummy round-robin index: the padding
            row / column), C <= 96; the warm start V0 is staged in LDS up to C = 78 and read from global memory above
   packed   upper triangle only, 97 <= C <= 112; an odd C guards every read / write of the dummy index; V0 from global
-  C > 112  refused by the four entry points -- but kb_create admits no handle of C > 111, so C = 111 is the largest
-           width that runs and neither C = 112 nor that refusal can be reached through the C-ABI
+  C > 112  beyond the capacity of k_marg's arrays (kMargMaxC) -- kb_create admits no handle of C > 111, so C = 111 is
+           the largest width that runs and C = 112 cannot be reached through the C-ABI
 regime() restates those three functions; test_marginal_cases.py asserts every row's regime, so a moved constant fails
 there and the table is redone.
 
@@ -26,7 +27,7 @@ PR, OR, EU, OM, DS, EQ, FV = (synth.PINHOLE_RADTAN, synth.OMNI_RADTAN, synth.EUC
                               synth.PINHOLE_EQUI, synth.PINHOLE_FOV)
 EPS = float(np.finfo(float).eps)
 
-# ---- kb_device.h / kb_kernels.hip, restated ----
+# ---- kb_solve_layout.h / kb_device.h, restated ----
 K_MARG_LDS_STAGE = 19000
 K_MARG_MAX_C = 112
 K_MARG_FULL_MAX_C = 96
@@ -47,8 +48,8 @@ def marg_lds_doubles(C):
     return (base + C * C if stage else base), stage
 
 
-# sizeof(ChainLds) (kb_kernels.hip, a static_assert beside the struct holds it to this): the gated tail's chains take
-# the start of the dynamic LDS
+# sizeof(ChainLds) (kb_solve_layout.h kChainLdsBytes; a static_assert beside the struct in kb_kernels.hip holds it to
+# this): the gated tail's chains take the start of the dynamic LDS
 CHAIN_LDS_BYTES = 8 * (16 * 12 + 64 * 12)
 # k_marg's own static LDS arrays as declared (doubles: dg, ap 2 x 112 each, wsort, tco 112 each, stat 4, nbase 16 x 7;
 # ints: perm 112), and what only full storage keeps (csr 2 x 112 doubles, prodkl, prodsel 64 ints each)
@@ -59,6 +60,18 @@ LDS_BYTES = 160 * 1024                     # per workgroup on gfx950
 
 def marg_lds_bytes(C):
     return max(8 * marg_lds_doubles(C)[0], CHAIN_LDS_BYTES)
+
+
+def marg_threads(C):
+    """one thread per 2 x 2 block of pairs (h (h + 1) / 2, h = ceil(C / 2)) and per (row of V, pair) (C h), in whole
+    waves, at most 1024"""
+    h = (C + 1) // 2
+    return min(-(-(h * (h + 1) // 2 + C * h) // 64) * 64, 1024)
+
+
+def marg_block(C):
+    """k_marg's block: full storage adds wave 0 for the rotations"""
+    return min(marg_threads(C) + (64 if marg_full(C) else 0), 1024)
 
 
 def regime(C):
@@ -93,8 +106,8 @@ ROWS = {r.C: r for r in (
     Row(107, (PR,) * 7 + (OR,), 24, PACKED, "packed, odd"),
     Row(111, (OR,) * 5 + (PR,) * 3, 24, PACKED, "the largest C a handle admits (kb_create), packed, odd"),
 )}
-# kMargMaxC = 112 and the entry points' own "C > 112" refusal cannot be reached through the C-ABI: kb_create admits
-# C <= 111 (the Schur tiles of k_schur), so these two rigs are refused there, by that name
+# kMargMaxC = 112 cannot be reached through the C-ABI: kb_create admits C <= 111 (the Schur tiles of k_schur), so these
+# two rigs are refused there, by that name
 K_CREATE_MAX_C = 111
 REFUSED_ROWS = {r.C: r for r in (
     Row(112, (OR,) * 6 + (PR, PR), 4, PACKED, "kMargMaxC: refused by kb_create"),

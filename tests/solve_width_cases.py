@@ -3,7 +3,8 @@ its code, as small rigs with their CPU references: shared by test_solve_width_ca
 the oracle and numpy alone) and test_gpu_solve_widths.py (the device against those references).  No GPU and no HIP
 import here.
 
-C = sum of intrinsics + 6 (N - 1) alone selects (kb_capi.hip kb_create, cov_cam_fn, kb_covariance; kb_kernels.hip):
+C = sum of intrinsics + 6 (N - 1) alone selects (kalibr_amd/csrc/kb_solve_layout.h, which kb_create, kb_covariance
+and the kernels read; the loops named below are kb_kernels.hip's):
   k_solve<CM> / k_cov_cam<CM>   one-wave register LDL^T on the packed S, CM = 16, 24, 32, 48, 64 for C <= CM;
                                 CM = 0 (the k_colimg tile image, blocked ldl_panels on MFMA) for C >= 65
   ldl_panels                    nb = (C + 16) >> 4 tile rows: 5 (65..79), 6 (80..95), 7 (96..111).  Panel 0 has nb - 1
@@ -14,8 +15,9 @@ C = sum of intrinsics + 6 (N - 1) alone selects (kb_capi.hip kb_create, cov_cam_
                                 threads, C > 64); the rounds step at 16/17, 32/33, 48/49, 64/65 (down) and 96/97
   k_cov_frames                  nks = (C + 3) >> 2 k-steps, nct = (C + 15) >> 4 column tiles, zero-padded operands
   k_build / k_buildp            the pipelined build for rigs of 4 .. 8 cameras
-The functions below restate those; test_solve_width_cases.py asserts every row's selectors against the table, so a moved
-constant fails there and the table is redone.
+The functions below restate those, independently of the header; test_solve_layout.py compares them with the header's
+figures at every admitted shape, and test_solve_width_cases.py asserts every row's selectors against the table, so a
+moved constant fails there and the table is redone.
 
 Every rig is synth.make_problem(models, 16, seed=20261200 + C, p_view=0.8).
 """
@@ -30,18 +32,18 @@ from kalibr_amd import synth
 PR, OR, EU, FV = synth.PINHOLE_RADTAN, synth.OMNI_RADTAN, synth.EUCM, synth.PINHOLE_FOV
 N_FRAMES, SEED0, P_VIEW = 16, 20261200, 0.8
 LDS_BYTES = 160 * 1024       # per workgroup on gfx950
-MAX_C = 111                  # kb_create: "camera block C > 111 not supported"
+MAX_C = 111                  # kb_solve_layout.h kMaxC; kb_create: "camera block C > 111 not supported"
 MAX_CAMS = 8                 # kb_create: 64 * wpb <= 512 threads of the build block (wpb = N for N >= 4)
-K_TS = 17                    # kb_kernels.hip kTS
+K_TS = 17                    # kb_solve_layout.h kTS
 K_TILE = 16 * K_TS           # kTileSz
-K_X_MAX_RANKS = 64           # kb_capi.hip kXMaxRanks: per-rank max|dx_f| slots of the image's aux area
-K_COV_WAVES = 4              # kb_kernels.hip kCovWaves
+K_X_MAX_RANKS = 64           # kXMaxRanks: per-rank max|dx_f| slots of the image's aux area
+K_COV_WAVES = 4              # kCovWaves
 K_COV_FRAMES = 2 * K_COV_WAVES
 
 
 # ---- the selectors, restated ----
 def solve_cm(C):
-    """the CM of k_solve<CM> / k_cov_cam<CM> (kb_create's fn_solve, cov_cam_fn); 0: the blocked factorisation"""
+    """the CM of k_solve<CM> / k_cov_cam<CM> (the header's solve_cm); 0: the blocked factorisation"""
     for cm in (16, 24, 32, 48, 64):
         if C <= cm:
             return cm
@@ -83,47 +85,70 @@ def cov_frames_steps(C):
 
 
 def build_kernel(N):
-    """kb_create's build_pipe: one wave per camera (nsplit == 1) and at most 8 cameras"""
+    """kb_create's build_pipe (kb_build_layout.h pipe_default): one wave per camera (nsplit == 1), at most 8 cameras"""
     return "k_buildp" if max(1, (4 + N - 1) // N) == 1 and N <= 8 else "k_build"
 
 
 # ---- dynamic LDS, restated (bytes) ----
 def lds_schur(C):
-    return 8 * 16 * 16 * nb(C)                                  # kb_capi.hip kb_create: sizeof(double) * 16 * CZ
+    return 8 * 16 * 16 * nb(C)                                  # P, Q [8][CZ], CZ = 16 nb
 
 
 def lds_camexp(N):
-    return 8 * (N * 256 + N * N * 36)                           # kb_create: h->lds_camexp
+    return 8 * (N * 256 + N * N * 36)                           # Hs [N][256] | T [N][N][36]
 
 
 def img_n(C):
-    return K_TILE * nb(C) * (nb(C) + 1) // 2 + 16 * nb(C) + 2 + K_X_MAX_RANKS   # kb_create: d.img_n
+    return K_TILE * nb(C) * (nb(C) + 1) // 2 + 16 * nb(C) + 2 + K_X_MAX_RANKS   # tiles | aux
 
 
 def lds_solve(N, C):
-    if C <= 64:                                                 # kb_create: h->lds_solve, the packed branch
+    if C <= 64:                                                 # the packed layout
         return 8 * (C * (C + 1) // 2 + 2 * C + 1 + N * 256 + 2 * N * N * 36) + 4 * C
     return 8 * (img_n(C) + 2 + 2 * nb(C) * K_TILE + 16 * nb(C)) + 4 * C     # the image branch
 
 
+def solve_offsets(N, C):
+    """where solve_body<CM> and k_cov_cam<CM> keep their ten regions, in doubles from the start of the dynamic LDS,
+    written down region after region from their lengths.  Packed (C <= 64): S [C(C+1)/2] | bv [C + 1] | gl [C] |
+    Hs [N][256] | T [N][N][36] | K [N][N][36] | ci; Dfac, Xinv, rDv are not there (they point at ci).  Image (C > 64): the
+    tiles | the aux area (bv = gl = Hs = T: g_c [16 nb], cost, rank 0's max|dx_f|) | Dfac [nb][tile] | Xinv [nb][tile] |
+    rDv [16 nb] | ci; K is not used (it points N * N * 36 doubles behind T)"""
+    if C <= 64:
+        S = 0
+        bv = S + C * (C + 1) // 2
+        gl = bv + (C + 1)
+        Hs = gl + C
+        T = Hs + N * 256
+        K = T + N * N * 36
+        ci = K + N * N * 36
+        return dict(S=S, bv=bv, gl=gl, Hs=Hs, T=T, K=K, Dfac=ci, Xinv=ci, rDv=ci, ci=ci)
+    tiles = K_TILE * nb(C) * (nb(C) + 1) // 2
+    Dfac = tiles + 16 * nb(C) + 1 + 1           # g_c slots, the cost, rank 0's max|dx_f|: an even count
+    Xinv = Dfac + nb(C) * K_TILE
+    rDv = Xinv + nb(C) * K_TILE
+    return dict(S=0, bv=tiles, gl=tiles, Hs=tiles, T=tiles, K=tiles + N * N * 36, Dfac=Dfac, Xinv=Xinv, rDv=rDv,
+                ci=rDv + 16 * nb(C))
+
+
 def lds_colimg(N, C):
-    return 8 * (N * 256 + 2 * N * N * 36) + 4 * C if C > 64 else 0          # kb_create: h->lds_colimg
+    return 8 * (N * 256 + 2 * N * N * 36) + 4 * C if C > 64 else 0          # Hs | K, T | ci
 
 
 def cov_eoff(N, C):
-    """doubles before k_cov_cam's second packed triangle (kb_covariance: eoff)"""
+    """doubles before k_cov_cam's second packed triangle (the header's cov_eoff)"""
     if C <= 64:
         return (lds_solve(N, C) + 15) // 16 * 2
     return K_TILE * nb(C) * (nb(C) + 1) // 2 + ((16 * nb(C) + 3) & ~1) + nb(C) * K_TILE
 
 
 def lds_cov_cam(N, C):
-    return max(lds_solve(N, C), 8 * (cov_eoff(N, C) + C * (C + 1) // 2))      # kb_covariance: lds_cam
+    return max(lds_solve(N, C), 8 * (cov_eoff(N, C) + C * (C + 1) // 2))
 
 
 def lds_cov_frames(C):
     nct = cov_frames_steps(C)[1]
-    return 8 * (C * C + K_COV_WAVES * 16 * (16 * nct + 1))                    # kb_covariance: lds_frames
+    return 8 * (C * C + K_COV_WAVES * 16 * (16 * nct + 1))
 
 
 def admitted_shapes():

@@ -45,8 +45,9 @@ figure is printed before it is asserted and the worst ratios at the module's end
 What the sweep found: at C = 95, 96 and 111 every marginal entry point failed with "invalid argument" from
 hipFuncSetAttribute -- the gated tail's chains (7.5 KB) were a static LDS array beside k_marg's own, and static +
 dynamic LDS passed 160 KB.  They now take the start of the dynamic LDS (marg_lds_bytes); the CPU check of the sizes is
-test_marginal_cases.py::test_k_marg_fits_the_lds_at_every_width.  kMargMaxC = 112 and the entry points' "C > 112"
-message cannot be reached: kb_create admits C <= 111, so the rigs of C = 112 and 113 are refused there.
+test_marginal_cases.py::test_k_marg_fits_the_lds_at_every_width.  kMargMaxC = 112 is the capacity of k_marg's arrays
+and no refusal of its own (kb_solve_layout.h asserts that it holds every admitted width): kb_create admits C <= 111, so
+the rigs of C = 112 and 113 are refused there.
 
 Not covered (no rig through the C-ABI produces them): marg_rot_wide, M1 = 1, kMargMaxSweeps exhaustion, KB_MARG_COLD
 (read once per process).  The cold restart after a non-finite result is: the zero-corner frame produces one.
@@ -336,7 +337,7 @@ def test_zero_corner_frame_fails_and_the_handle_recovers(capi):
 
 @pytest.mark.parametrize("C", list(MC.REFUSED_ROWS))
 def test_widths_beyond_the_handle_are_refused_by_name(capi, C):
-    """kMargMaxC = 112 and the marginal entry points' own "C > 112" refusal are out of reach: kb_create admits
+    """kMargMaxC = 112 is out of reach (the marginal entry points have no width refusal of their own): kb_create admits
     C <= 111"""
     with pytest.raises(capi.KbError, match="C > 111"):
         capi.Solver(MC.problem_of(MC.REFUSED_ROWS[C]))

@@ -25,8 +25,9 @@ max|V^T V - I|, max off-diagonal |V^T Omega V| / sv_0 (worst over the variants).
     107   88 / 106 /  94 / 88   0.041       2.2e-15  4.7e-13  7.6e-12  1.1e-06  5.0e-13  6.2e-14  1.4e-15
     111   84 / 106 /  96 / 84   0.025       3.4e-15  2.3e-12  7.8e-11  1.6e-07  2.1e-12  6.7e-14  2.6e-15
 
-C = 111 stands where kMargMaxC = 112 would: kb_create admits no handle of C > 111, so 112 cannot run (the two refused
-rigs of the table, C = 112 and 113, are refused there).
+C = 111 stands where kMargMaxC = 112 (the capacity of k_marg's arrays) would: kb_create admits no handle of C > 111, so
+112 cannot run (the two refused rigs of the table, C = 112 and 113, are refused there; the marginal entry points
+refuse no width themselves).
 
 At the state after one GN step (the warm chains' second state, variant (a); C = 23, 79, 107): ranks 22, 66, 88, margins
 0.41, 0.18, 0.24, x spread 2.7e-13 .. 8.8e-13.  The device-loop rigs (C = 79, 97): 4 iterations each, ranks 66 and 81 in
@@ -44,6 +45,7 @@ import pytest
 from oracle import oracle as O
 
 from . import marginal_cases as MC
+from .test_solve_layout import header_constants
 
 # bounds on the reference spread, a factor 10 or so above the table in the docstring: the oracle and LAPACK are the two
 # referees of the GPU module, and its bars assume they agree to this
@@ -107,6 +109,9 @@ def test_k_marg_fits_the_lds_at_every_width(tmp_path):
         assert MC.marg_lds_bytes(C) + static[MC.marg_full(C)] <= MC.LDS_BYTES, C
     # as wide as the kernel's own limit, which no handle reaches
     assert MC.marg_lds_bytes(MC.K_MARG_MAX_C) + static[False] <= MC.LDS_BYTES
+    # kb_solve_layout.h's marg_fits adds this bound to the dynamic size: both instances are within it
+    bound = header_constants(tmp_path)["st_marg"]
+    assert max(static.values()) <= bound, (static, bound)
 
 
 @pytest.mark.parametrize("C", list(MC.ROWS) + list(MC.REFUSED_ROWS))

@@ -44,6 +44,7 @@ import numpy as np
 import pytest
 
 from . import solve_width_cases as W
+from .test_solve_layout import header_constants
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SLICE_CASES = [(C, lam) for C in W.SLICE_ROWS for lam in W.lambdas(C)]
@@ -236,8 +237,9 @@ def _static_lds(tmp_path):
 
 
 def test_solve_and_covariance_kernels_fit_the_lds_at_every_width(tmp_path):
-    """static + dynamic LDS within the 160 KB of a workgroup for every N and C a handle admits: kb_create and
-    kb_covariance check the dynamic size alone, and beyond 160 KB hipFuncSetAttribute refuses the launch"""
+    """static + dynamic LDS within the 160 KB of a workgroup for every N and C a handle admits (beyond 160 KB
+    hipFuncSetAttribute refuses the launch), and each kernel's static LDS within the bound that kb_create and
+    kb_covariance add to the dynamic size (kb_solve_layout.h)"""
     st = _static_lds(tmp_path)
     print("static LDS:", {f"{k}<{a}>" if a is not None else k: v for (k, a), v in sorted(st.items(), key=str)})
     cms = (0, 16, 24, 32, 48, 64)
@@ -270,48 +272,28 @@ def test_solve_and_covariance_kernels_fit_the_lds_at_every_width(tmp_path):
         print(f"{k}: {v} B at N = {N}, C = {C} ({W.LDS_BYTES - v} B to spare)")
         assert v <= W.LDS_BYTES, (k, v, N, C)
     assert len(worst) == 6 + 6 + 3 + 3
+    # kb_create and kb_covariance add kb_solve_layout.h's static bounds to the dynamic sizes: each kernel's real static
+    # LDS is within its family's bound
+    k = header_constants(tmp_path)
+    for (kern, arg), size in sorted(st.items(), key=str):
+        bound = k["st_" + kern[2:]]
+        print(f"{kern}<{arg}>: static {size} B, bound {bound} B")
+        assert size <= bound, (kern, arg)
     # the figure this check was asked for: k_cov_frames at the widest C
     assert W.lds_cov_frames(111) == 156424
 
 
-# the C-ABI reports no LDS size, so each restated formula and selector is held to the text it restates
+# The host's formulas and selectors (kb_create, kb_covariance) are kb_solve_layout.h's, compared value by value with the
+# restatements in test_solve_layout.py.  What the kernels alone decide stays held to their text: the loops of
+# ldl_panels and cov_invert_columns, and k_buildp's camera count (kTS, kTileSz, kCovWaves and k_cov_frames' nct / nks
+# moved into the header: compared as numbers there)
 SOURCE_TEXT = {
-    "kb_capi.hip": (
-        "if (h->C > 111) {",                                                                  # kb_create
-        "if (64 * d.wpb > 512) {",
-        "h->build_pipe = d.nsplit == 1 && h->N <= kBuildpMaxCams;",
-        "const int CZ = 16 * ((C + 16) / 16);",
-        "h->lds_camexp = sizeof(double) * (N * 256 + N * N * 36);",                          # lds_camexp
-        "h->lds_schur = sizeof(double) * 16 * CZ;",                                           # lds_schur
-        "h->lds_solve = sizeof(double) * (C * (C + 1) / 2 + 2 * C + 1 + N * 256 + 2 * N * N * 36) + sizeof(int) * C;",
-        "const int nb = (C + 16) / 16, n16 = 16 * nb;",
-        "d.img_n = kTileSz * nb * (nb + 1) / 2 + n16 + 2 + kXMaxRanks;",                     # img_n
-        "h->lds_solve = sizeof(double) * (d.img_n + 2 + 2 * nb * kTileSz + n16) + sizeof(int) * C;",  # lds_solve
-        "h->lds_colimg = sizeof(double) * (N * 256 + 2 * N * N * 36) + sizeof(int) * C;",    # lds_colimg
-        "h->solve_threads = C <= 64 ? 256 : 512;",
-        "h->fn_solve = C <= 16 ? (const void*)k_solve<16> : C <= 24 ? (const void*)k_solve<24> : C <= 32 ? "
-        "(const void*)k_solve<32> : C <= 48 ? (const void*)k_solve<48> : C <= 64 ? (const void*)k_solve<64> : "
-        "(const void*)k_solve<0>;",                                                           # solve_cm
-        "return C <= 16 ? (const void*)k_cov_cam<16> : C <= 24 ? (const void*)k_cov_cam<24> : C <= 32 ? "
-        "(const void*)k_cov_cam<32> : C <= 48 ? (const void*)k_cov_cam<48> : C <= 64 ? (const void*)k_cov_cam<64> : "
-        "(const void*)k_cov_cam<0>;",
-        "const int nbz = (h->C + 16) / 16, ntiles = nbz * (nbz + 1) / 2; const int ts = (ntiles + 3) / 4; "
-        "h->ms = ts <= 1 ? 1 : ts <= 4 ? 4 : 7;",                                             # schur_ms
-        "const int nct = (C + 15) / 16;",                                                     # kb_covariance
-        "const size_t lds_frames = sizeof(double) * ((size_t)C * C + (size_t)kCovWaves * 16 * (16 * nct + 1));",
-        "const int eoff = C <= 64 ? (int)((h->lds_solve + 15) / 16) * 2 : kTileSz * nb16 * (nb16 + 1) / 2 + "
-        "((16 * nb16 + 3) & ~1) + nb16 * kTileSz;",                                           # cov_eoff
-        "const size_t lds_cam = std::max(h->lds_solve, sizeof(double) * ((size_t)eoff + (size_t)C * (C + 1) / 2));",
-        "constexpr int kXMaxRanks = 64;",
-    ),
     "kb_kernels.hip": (
-        "constexpr int kTS = 17;", "constexpr int kTileSz = 16 * kTS;", "constexpr int kBuildpMaxCams = 8;",
-        "constexpr int kCovWaves = 4, kCovFrames = 2 * kCovWaves;",
+        "constexpr int kBuildpMaxCams = 8;",
         "const int nf = (nb - 1 - q) > 4 ? 2 : 1;",                                           # factor_waves
         "const int ti = q + 1 + 4 * fw + t;",
         "const int tid = threadIdx.x, grp = tid >> 4, r = tid & 15, ngrp = nth >> 4;",        # cov_rounds
         "for (int j0 = 0; j0 < C; j0 += ngrp) {",
-        "const int nct = (C + 15) >> 4, nks = (C + 3) >> 2, LDT = 16 * nct + 1;",             # cov_frames_steps
     ),
 }
 
