@@ -504,10 +504,37 @@ int kb_sp_get_system(kb_sp_handle* h, double* Hcc, double* Hsc, double* Hband, d
  * outside the spline interval is refused before any launch. */
 int kb_sp_covariance(kb_sp_handle* h, double* Ptt, double* Pst, double* Pband, int* ok);
 int kb_sp_curve_covariance(kb_sp_handle* h, int32_t n, const double* times, double* P, int* ok);
-/* Optimizer2::optimize over the spline system (LM policy 0 / GN policy 1), host-driven loop over the
- * device passes; trace as kb_get_trace. */
+/* Optimizer2::optimize over the spline system (Optimizer2.cpp:183-273; LM policy 0, GN policy 1, DogLeg policy 2; any
+ * other value runs as GN), host-driven loop over the device passes; trace as kb_get_trace.
+ * Policy 2 (DogLegTrustRegionPolicy.cpp:11-161 as restated above kb_set_dogleg_options, both deviations included;
+ * options: kb_sp_set_dogleg_options): a pass is the build (only after an accepted step) with the
+ * steepest-descent reduction, the GN solve at lambda = 0 without any conditioner (only when the SD branch is not taken
+ * and no GN step of this system is held) with the step dots, then dx = a g + b dx_gn, the update and the candidate's
+ * cost, all on the device; the policy arithmetic runs on the host in double and only the scalar block is read back
+ * (up to three times per pass).  A rejected step is followed by a pass that neither builds, reduces nor solves; a
+ * failed solve is a failed iteration without a step.  g and H are what kb_sp_build made: robust weights, motion and
+ * prior terms are part of them and of the cost.  The lambda column of kb_sp_get_trace carries delta. */
 int kb_sp_optimize(kb_sp_handle* h, const kb_optimizer_options* opts, kb_solution* out);
 int kb_sp_get_trace(kb_sp_handle* h, double* trace, int32_t cap);
+/* LinearSystemSolver::rhsJtJrhs (LinearSystemSolver.hpp:66-69; SparseCholeskyLinearSystemSolver.cpp:106-111) of the
+ * last kb_sp_build, on the device from the node blocks and the camera block: g^T H g with g = [g_theta | g_s] of
+ * kb_sp_get_rhs and H of kb_sp_get_system (no conditioner).  Fails with "kb_sp_rhs_jtj_rhs: build first" otherwise. */
+int kb_sp_rhs_jtj_rhs(kb_sp_handle* h, double* out);
+/* options of policy 2 for the following kb_sp_optimize calls (kb_set_dogleg_options' struct and rules: delta_init is
+ * what optimizationStarting, DogLegTrustRegionPolicy.cpp:11-22, assigns to delta); NULL selects the defaults */
+int kb_sp_set_dogleg_options(kb_sp_handle* h, const kb_dogleg_options* opts);
+/* One solveSystemImplementation (DogLegTrustRegionPolicy.cpp:63-137) of the last kb_sp_build for trust radius delta, as
+ * kb_dogleg_step: the steepest-descent reduction (:70-75), the GN solve (:92-102; lambda = 0, no conditioner; only when
+ * the SD branch of :82 is not taken), the selection and the step dx_out [C + 6K] (may be NULL).  delta == 0 applies the
+ * first-iteration rule (:105-107); a negative or non-finite delta is refused.  *ok = 0 exactly when a needed solve
+ * fails (dx_out untouched, info holds the SD quantities, step_type -1).  A query: the state is untouched; where it
+ * solved, dx, the solved flag and the scalars are as a kb_sp_solve at lambda = 0 leaves them, where it did not they stay
+ * as they were.  L0_over_J is relative to the build's cost.  Needs kb_sp_build. */
+int kb_sp_dogleg_step(kb_sp_handle* h, double delta, double* dx_out, kb_dogleg_info* info, int* ok);
+/* Per-pass dog-leg trace of the last kb_sp_optimize with policy 2 (empty after any other policy), aligned with
+ * kb_sp_get_trace: [delta, step_type (-1: failed solve), beta, L0, dx_sd_norm, dx_gn_norm] x n (returns count)
+ * (_delta, _stepType, _beta, _L0, _dx_sd_norm, _dx_gn_norm of DogLegTrustRegionPolicy.hpp). */
+int kb_sp_get_dogleg_trace(kb_sp_handle* h, double* out, int32_t cap);
 /* Benchmark: exactly n_iter GN passes (build + solve + update + cost), captured in a hipGraph. */
 int kb_sp_run_gn_iterations(kb_sp_handle* h, int32_t n_iter, double* seconds);
 /* Per-kernel device time (ms, HIP events on the handle's stream) of one GN pass, averaged over n passes:
@@ -529,7 +556,7 @@ int kb_sp_assemble_stats(kb_sp_handle* h, int32_t n, double* ms, double* bytes);
  * computeEpsilon needs the chi^2 quantile of the term's dimension, which has no closed form for the IMU families
  * (df = 3), so it is the caller's to compute.
  * A handle with any estimator != NONE or an invR set is "weighted": kb_sp_eval_cost, kb_sp_build, kb_sp_get_system,
- * kb_sp_get_rhs, kb_sp_solve, kb_sp_optimize (LM and GN), kb_sp_run_gn_iterations, kb_sp_kernel_stats and
+ * kb_sp_get_rhs, kb_sp_solve, kb_sp_optimize (every policy), kb_sp_rhs_jtj_rhs, kb_sp_dogleg_step, kb_sp_run_gn_iterations, kb_sp_kernel_stats and
  * kb_sp_assemble_stats work on it through the same calls.  kb_sp_covariance inverts the weighted system as built: there is no
  * build without the estimator, so a covariance without it needs the estimators cleared first.  Every setter voids the built system and the captured GN pass; a refused call leaves the
  * handle as it was; a handle whose settings are all cleared launches exactly the kernels of a fresh one.

@@ -38,6 +38,8 @@ EXPORTS = [
     "kb_sp_solve", "kb_sp_get_rhs", "kb_sp_apply_update", "kb_sp_revert", "kb_sp_get_system", "kb_sp_optimize",
     "kb_sp_get_trace", "kb_sp_run_gn_iterations", "kb_sp_kernel_stats", "kb_sp_assemble_stats", "kb_sp_set_motion_error",
     "kb_sp_set_position_priors", "kb_sp_covariance", "kb_sp_curve_covariance",
+    # dog-leg policy on the spline path
+    "kb_sp_rhs_jtj_rhs", "kb_sp_set_dogleg_options", "kb_sp_dogleg_step", "kb_sp_get_dogleg_trace",
     # robust terms on the spline path (kb_sp_set_corner_invR is in EXPORTS_MIXED_CASE below)
     "kb_sp_set_mestimator", "kb_sp_get_mestimator_weights",
 ]
@@ -220,6 +222,10 @@ def lib():
         L.kb_sp_get_mestimator_weights.argtypes = [C.c_void_p, C.c_int32, dp, dp]
         L.kb_sp_covariance.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_int)]
         L.kb_sp_curve_covariance.argtypes = [C.c_void_p, C.c_int32, dp, dp, C.POINTER(C.c_int)]
+        L.kb_sp_rhs_jtj_rhs.argtypes = [C.c_void_p, dp]
+        L.kb_sp_set_dogleg_options.argtypes = [C.c_void_p, C.POINTER(DoglegOptions)]
+        L.kb_sp_dogleg_step.argtypes = [C.c_void_p, C.c_double, dp, C.POINTER(DoglegInfo), C.POINTER(C.c_int)]
+        L.kb_sp_get_dogleg_trace.argtypes = [C.c_void_p, dp, C.c_int32]
         _lib = L
     return _lib
 
@@ -747,8 +753,14 @@ class SplineSolver:
         _check(lib().kb_sp_curve_covariance(self.h, t.size, _d(t), _d(P), C.byref(ok)))
         return bool(ok.value), P
 
-    def optimize(self, policy="gn", lambda0=10.0, max_iterations=20, eps_x=1e-3, eps_j=1.0):
-        o = OptimizerOptions(0 if policy == "lm" else 1, lambda0, max_iterations, eps_x, eps_j, 1, 0)
+    def optimize(self, policy="gn", lambda0=10.0, max_iterations=20, eps_x=1e-3, eps_j=1.0, delta_init=0.0):
+        """kb_sp_optimize: policy "lm", "dogleg" or "gn" (any other string is "gn" as before).  "dogleg": delta_init
+        is the initial trust radius (kb_sp_set_dogleg_options), res["trace"]'s lambda column carries delta and
+        res["dogleg_trace"] holds per pass [delta, step_type, beta, L0, dx_sd_norm, dx_gn_norm]."""
+        pol = {"lm": 0, "dogleg": 2}.get(policy, 1)
+        if pol == 2:
+            _check(lib().kb_sp_set_dogleg_options(self.h, C.byref(DoglegOptions(float(delta_init)))))
+        o = OptimizerOptions(pol, lambda0, max_iterations, eps_x, eps_j, 1, 0)
         s = Solution()
         _check(lib().kb_sp_optimize(self.h, C.byref(o), C.byref(s)))
         res = {f: getattr(s, f) for f, _ in Solution._fields_}
@@ -756,7 +768,27 @@ class SplineSolver:
         tr = np.zeros((cap, 4))
         n = _check(lib().kb_sp_get_trace(self.h, _d(tr), cap))
         res["trace"] = tr[:n].copy()
+        if pol == 2:
+            dt = np.zeros((cap, 6))
+            n = _check(lib().kb_sp_get_dogleg_trace(self.h, _d(dt), cap))
+            res["dogleg_trace"] = dt[:n].copy()
         return res
+
+    def rhs_jtj_rhs(self):
+        """kb_sp_rhs_jtj_rhs after build(): rhs^T H rhs of the built system (no conditioner)"""
+        v = C.c_double()
+        _check(lib().kb_sp_rhs_jtj_rhs(self.h, C.byref(v)))
+        return v.value
+
+    def dogleg_step(self, delta):
+        """kb_sp_dogleg_step after build(): (ok, dx, info) of one dog-leg step selection for trust radius delta
+        (0: the first-iteration rule).  info: step_type (0 SD, 1 GN, 2 DL), delta as used, beta, sd_scale, dx_sd_norm,
+        dx_gn_norm, L0_over_J."""
+        dx = np.zeros(self.ncols)
+        ok = C.c_int(0)
+        inf = DoglegInfo()
+        _check(lib().kb_sp_dogleg_step(self.h, float(delta), _d(dx), C.byref(inf), C.byref(ok)))
+        return bool(ok.value), dx, {f: getattr(inf, f) for f, _ in DoglegInfo._fields_}
 
     def run_gn(self, n_iter):
         sec = C.c_double()

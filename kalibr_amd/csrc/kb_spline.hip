@@ -79,7 +79,10 @@ constexpr int IRQ = 42;     // IMU record: T1 [9] | T2 [9] | T3 [9] | C^T [9] | 
 constexpr int IRS = IRQ + 13;  // LDS stride of a staged IMU record: record | w0 w1 w2 [12] | pad
 constexpr int PNS = 8;      // IMU samples per k_sp_assemble operand panel (48 residual rows = 12 MFMA k-steps)
 constexpr int PST = 49;     // LDS row stride of the panel (48 columns: Jw [36] | J_theta [9] | -e | 0 0)
-enum { SC_COST_BUILD = 0, SC_OK = 1, SC_DX = 2, SC_COST = 3, SC_LAM2 = 4, SC_NSC = 8 };
+// SC_GHG .. SC_GGN: the dog-leg policy's sums (kb_spline_dogleg.hip): g^T H g, g.g | dx_gn.dx_gn, g.dx_gn (each pair
+// written by one k_sp_dl_sum in the order of its partial pairs)
+enum { SC_COST_BUILD = 0, SC_OK = 1, SC_DX = 2, SC_COST = 3, SC_LAM2 = 4, SC_GHG = 5, SC_GG = 6, SC_GN2 = 7, SC_GGN = 8,
+       SC_NSC = 12 };
 
 struct SpDev {
   int N, C, K, F, M, n, m, n_target;
@@ -3326,6 +3329,11 @@ __global__ void __launch_bounds__(64) k_sp_cov_curve(SpDev d) {
 
 }  // namespace ksp
 
+// the dog-leg policy's kernels (kb_sp_optimize policy 2, kb_sp_dogleg_step, kb_sp_rhs_jtj_rhs)
+#define KSP_DL_DEVICE
+#include "kb_spline_dogleg.hip"
+#undef KSP_DL_DEVICE
+
 // ==================================================================================================
 // host side
 // ==================================================================================================
@@ -3486,6 +3494,12 @@ struct kb_sp_handle {
   bool cov_ready = false;
   const void* fn_covcam = nullptr;
   size_t lds_cprep = 0, lds_clevel = 0;
+  // dog-leg policy (kb_spline_dogleg.hip): buffers made by the first call that needs them, options, per-pass trace
+  bool dl_ready = false;
+  SpDl dl{};
+  kb_dogleg_options dl_opts{0.0};
+  std::vector<double> dl_trace;
+  std::vector<double> dl_pass_ms;  // diagnostics only: host wall time per pass
 
   template <class T>
   int alloc(T** p, size_t cnt) {
@@ -4494,6 +4508,11 @@ int kb_sp_get_system(kb_sp_handle* h, double* Hcc, double* Hsc, double* Hband, d
 
 }  // extern "C"
 
+// the dog-leg policy's host side: sp_dl_optimize (kb_sp_optimize policy 2) and the kb_sp_*dogleg* / kb_sp_rhs_jtj_rhs entries
+#define KSP_DL_HOST
+#include "kb_spline_dogleg.hip"
+#undef KSP_DL_HOST
+
 namespace {
 // the checks of a covariance query and, on the first one, its buffers and launch sizes
 int cov_prepare(kb_sp_handle* h, const char* who) {
@@ -4627,6 +4646,8 @@ int kb_sp_optimize(kb_sp_handle* h, const kb_optimizer_options* o, kb_solution* 
   // Optimizer2::optimize (Optimizer2.cpp:183-273) + LM / GN policies, host-driven over the device passes
   std::memset(out, 0, sizeof(*out));
   h->trace.clear();
+  h->dl_trace.clear();
+  if (o->policy == 2) return sp_dl_optimize(h, o, out);  // DogLeg (kb_spline_dogleg.hip)
   const bool lm = o->policy == 0;
   const int ncols = h->ncols;
   std::vector<double> dx(ncols, 0.0), rhs(ncols, 0.0), tmp(ncols);
