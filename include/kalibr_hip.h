@@ -76,6 +76,10 @@ int kb_set_state(kb_handle* h, const double* poses_q, const double* poses_t, con
                  const double* intrinsics);
 int kb_set_state_flat(kb_handle* h, const double* state);
 int kb_get_state_flat(kb_handle* h, double* state);
+/* Diagnostics, read-only: the camera chains the device keeps beside a state buffer.  which = 0: of the current state,
+ * 1: of the other buffer (the last candidate).  L_out [n_cams][12]: L_i = B_{i-1} .. B_0 as R (9, row-major) | t (3);
+ * K_out [n_cams][n_cams][36]: K_{i,j}, 6 x 6 row-major, zero for j >= i.  Either pointer may be null. */
+int kb_debug_chains(kb_handle* h, int which, double* L_out, double* K_out);
 int kb_state_size(const kb_handle* h);
 int kb_num_cols(const kb_handle* h);     /* JCols = C + 6F */
 int kb_camera_cols(const kb_handle* h);  /* C = sum(intrinsics) + 6(N-1) */

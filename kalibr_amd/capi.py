@@ -23,7 +23,7 @@ dp = C.POINTER(C.c_double)
 # every symbol declared in include/kalibr_hip.h
 EXPORTS = [
     "kb_create", "kb_destroy", "kb_last_error", "kb_upload_observations", "kb_set_state", "kb_set_state_flat",
-    "kb_get_state_flat", "kb_state_size", "kb_num_cols", "kb_camera_cols", "kb_eval_cost", "kb_build",
+    "kb_get_state_flat", "kb_debug_chains", "kb_state_size", "kb_num_cols", "kb_camera_cols", "kb_eval_cost", "kb_build",
     "kb_set_constant_conditioner", "kb_set_conditioner", "kb_solve", "kb_get_rhs", "kb_rhs_jtj_rhs", "kb_covariance", "kb_reprojection_error_stats", "kb_apply_update", "kb_revert", "kb_get_normal_blocks",
     "kb_optimize", "kb_get_trace", "kb_set_dogleg_options", "kb_dogleg_step", "kb_get_dogleg_trace", "kb_run_gn_iterations", "kb_gn_prepare", "kb_gn_launch", "kb_build_kernel_stats",
     "kb_build_kernel_name", "kb_build_viewtab", "kb_comm_get_unique_id", "kb_gn_pass_times", "kb_append_frames", "kb_drop_last_frames", "kb_optimize_marginal", "kb_optimize_marginal_analyze",
@@ -149,6 +149,7 @@ def lib():
                                              C.c_void_p]
         L.kb_set_state_flat.argtypes = [C.c_void_p, dp]
         L.kb_get_state_flat.argtypes = [C.c_void_p, dp]
+        L.kb_debug_chains.argtypes = [C.c_void_p, C.c_int, dp, dp]
         L.kb_set_state.argtypes = [C.c_void_p, dp, dp, dp, dp]
         for n in ("kb_state_size", "kb_num_cols", "kb_camera_cols", "kb_revert"):
             getattr(L, n).argtypes = [C.c_void_p]
@@ -297,6 +298,14 @@ class Solver:
         st = np.zeros(self.S)
         _check(lib().kb_get_state_flat(self.h, _d(st)))
         return st
+
+    def debug_chains(self, which=0):
+        """Diagnostics: the camera chains (L [N, 12], K [N, N, 6, 6]) kept beside the current state (which = 0) or
+        beside the other state buffer (1)."""
+        n = self.prob.n_cams
+        L, K = np.zeros((n, 12)), np.zeros((n, n, 6, 6))
+        _check(lib().kb_debug_chains(self.h, int(which), _d(L), _d(K)))
+        return L, K
 
     def eval_cost(self):
         J = C.c_double()

@@ -652,6 +652,8 @@ kb_handle* kb_create(const kb_layout* L) {
   rc |= h->alloc(&tgt, 3 * (size_t)h->K);
   rc |= h->alloc(&d.state, 2 * (size_t)d.S);
   rc |= h->alloc(&d.camL, 2 * 12 * (size_t)h->N);  // [2] slots: ping-pong with the state buffers
+  // the only allocation of the chain buffers (no path resizes them: they depend on N alone).  alloc() zero-fills, and
+  // chain_write relies on it: the blocks K_{i,j}, j >= i, of both slots are never written again
   rc |= h->alloc(&d.camK, 2 * 36 * (size_t)h->N * h->N);
   rc |= h->alloc(&d.Hff, 36 * (size_t)h->F);
   rc |= h->alloc(&d.Hfc, 6 * (size_t)h->C * h->F);
@@ -1038,6 +1040,19 @@ int kb_get_state_flat(kb_handle* h, double* state) {
   KB_HIP(hipSetDevice(h->device));
   KB_HIP(hipMemcpyAsync(state, h->d.state + (size_t)h->cur * h->d.S, sizeof(double) * h->S, hipMemcpyDeviceToHost,
                         h->stream));
+  KB_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int kb_debug_chains(kb_handle* h, int which, double* L_out, double* K_out) {
+  if (!h || which < 0 || which > 1) return fail("kb_debug_chains: bad arguments");
+  KB_HIP(hipSetDevice(h->device));
+  const int slot = which ? 1 - h->cur : h->cur;
+  const size_t nl = 12 * (size_t)h->N, nk = 36 * (size_t)h->N * h->N;
+  if (L_out)
+    KB_HIP(hipMemcpyAsync(L_out, h->d.camL + slot * nl, sizeof(double) * nl, hipMemcpyDeviceToHost, h->stream));
+  if (K_out)
+    KB_HIP(hipMemcpyAsync(K_out, h->d.camK + slot * nk, sizeof(double) * nk, hipMemcpyDeviceToHost, h->stream));
   KB_HIP(hipStreamSynchronize(h->stream));
   return 0;
 }

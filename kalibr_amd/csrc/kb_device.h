@@ -166,8 +166,13 @@ struct KbDev {
       if ((i) == 0 || (i) == 7) (d).dbg_ts[60 + ((i) == 7)] = __builtin_amdgcn_s_memtime(); \
     }                                                                                    \
   } while (0)
+// the same by lane 0 of whichever wave calls it (k_solve's update, pair-product and chain-writing waves: slots 128 ..)
+#define KB_TSW(d, i)                                                                           \
+  do {                                                                                         \
+    if ((threadIdx.x & 63) == 0 && (d).dbg_ts) (d).dbg_ts[i] = __builtin_amdgcn_s_memrealtime(); \
+  } while (0)
 // build-kernel timeline (k_buildp): lane 0 of the calling wave of block 0 stamps slot 64 + i
-#define KB_TSB(d, i)                                                                                        \
+#define KB_TSB(d, i)                                                                                       \
   do {                                                                                                      \
     if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && (d).dbg_ts) (d).dbg_ts[64 + (i)] = __builtin_amdgcn_s_memrealtime(); \
   } while (0)
@@ -184,6 +189,9 @@ struct KbDev {
   do {               \
   } while (0)
 #define KB_TSB(d, i) \
+  do {               \
+  } while (0)
+#define KB_TSW(d, i) \
   do {               \
   } while (0)
 #define KB_STAMP(d, i) \

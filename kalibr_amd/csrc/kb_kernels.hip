@@ -445,7 +445,9 @@ __device__ __forceinline__ void chain_pairs(const KbDev& d, const double* base, 
     for (int e = 0; e < 3; ++e) L.PR[q][9 + e] = Qt[e];
   }
 }
-// part 2 (after a barrier that follows part 1): L_i and K_{i,j} into slot `slot`
+// part 2 (after a barrier, or a flag, that follows part 1): L_i and K_{i,j}, j < i, into slot `slot`.  The structural
+// zeros K_{i,j}, j >= i, are never written: both slots of camK are zero from their allocation (kb_create) and every
+// reader that stages all N N 36 entries (k_colimg, solve_stage, k_build's round 2) finds them there
 __device__ __forceinline__ void chain_write(const KbDev& d, const ChainLds& L, int slot, int tx, int nth) {
   const int N = d.N;
   double* Lo = cam_L(d, slot);
@@ -454,14 +456,10 @@ __device__ __forceinline__ void chain_write(const KbDev& d, const ChainLds& L, i
     const int i = q / 12, e = q % 12;
     Lo[q] = L.PR[i * (i + 1) / 2][e];
   }
-  for (int idx = tx; idx < N * N * 36; idx += nth) {
-    const int e = idx % 36, ij = idx / 36, i = ij / N, j = ij % N;
-    double val = 0.0;
-    if (j < i) {
-      const double* P = L.PR[i * (i + 1) / 2 + j + 1];
-      val = -chain_entry(P, P + 9, L.st[j], e / 6, e % 6);
-    }
-    Ko[idx] = val;
+  for (int idx = tx; idx < N * (N - 1) / 2 * 36; idx += nth) {  // pair (i, j), j < i, at i (i - 1) / 2 + j
+    const int e = idx % 36, pr = idx / 36, i = tri_row(pr) + 1, j = pr - i * (i - 1) / 2;
+    const double* P = L.PR[i * (i + 1) / 2 + j + 1];
+    Ko[(i * N + j) * 36 + e] = -chain_entry(P, P + 9, L.st[j], e / 6, e % 6);
   }
 }
 __device__ __forceinline__ void chain_block(const KbDev& d, const double* base, int slot, int nth) {
@@ -3410,10 +3408,14 @@ __device__ __forceinline__ int cidx(int i, int j, int C) { return j * (2 * C - j
 //   Step k reads the current row k from lane k of the lane's own 16-lane row by DPP, so the diagonal factor and the
 //   panel's triangular solve are one 16-step register loop.
 // Before that, every wave applies panel q-1 to a tile of column q on v_mfma_f64_16x16x4f64; while the factor waves run,
-// 4 "update" waves apply panel q-1 to the remaining trailing tiles (i, j), j > q (ldl_panels).  The 106-pivot chain
-// runs on the factor waves only.
+// the "update" waves prepare the next column only (left-looking): the tiles (i, q+1) get the panels 0 .. q-1, each tile
+// on one wave, in panel order (ldl_panels; the items: kb_solve_layout.h).  Nothing is updated before the panel after
+// next needs it (one tile but one phase early, where a wave is idle), and no panel waits for its update waves: the
+// right-looking schedule's first update, 15 tile products beside panel 1 at C = 106, outlasted that panel's factor by
+// 0.9 us.  The 106-pivot chain runs on the factor waves only.
 // Same algebra as the scalar right-looking LDL^T (SparseCholeskyLinearSystemSolver.cpp:48-89 / Cholmod(impl).hpp:
-// 387-399 factor the same matrix); only the accumulation order of the trailing updates differs.
+// 387-399 factor the same matrix); only the accumulation order of the trailing updates differs: every tile takes one
+// product per panel, each from a zero accumulator, subtracted in panel order (as the right-looking schedule did).
 // ---------------------------------------------------------------------------------------------
 
 // LDS index of lower entry (i, j), i >= j, of the staged camera block: packed column-major (CM > 0) or tiles
@@ -3607,14 +3609,20 @@ __device__ __forceinline__ void tile_unit_inverse2(const double* Dfac, const dou
 // the factorisation (every thread of the 8-wave block calls it); two phases per panel q:
 //   A (q > 0): column q of the trailing matrix gets panel q-1 (tiles (q + w, q), one per wave w, on MFMA);
 //   B: factor waves 0 (and 1 while panel q has more than four tiles below it) factor panel q; update waves 2, 3, 6, 7
-//      apply panel q-1 to the remaining trailing tiles (i, j), j > q (waves 4 and 5 share the factor waves' SIMDs and
-//      stay idle so that the MFMA tiles do not slow the pivot chain); wave 7 then inverts the previous panel's factored
-//      diagonal tile (Xinv, for the backsolve's mat-vecs).
+//      apply the panels 0 .. q-1 to column q + 1, the tiles (i, q + 1), q < i < nb: q (nb - 1 - q) tile products, and
+//      the last diagonal tile's one phase early: for nb = 7 5, 8, 9, 12, 1 at q = 1 .. 5, one tile and at most four
+//      products on a wave (at q = 1: two tiles on wave 2).  Waves 4 and 5 share the factor waves' SIMDs and stay off
+//      the MFMA pipe while those factor, so that the tiles do not slow the pivot chain; once wave 0 factors alone,
+//      wave 5 (SIMD 1) is a fifth update wave.  Waves 1 and 5 invert the factored diagonal tiles (Xinv, for the
+//      backsolve's mat-vecs).
 // okl is cleared on a non-positive real pivot.
 __device__ __forceinline__ void ldl_panels(const KbDev& d, double* S, double* rD, double* Dfac, double* Xinv, int C, int nb,
                                            int* okl) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ow = wave == 2 ? 0 : wave == 3 ? 1 : wave == 6 ? 2 : wave == 7 ? 3 : -1;
+  // the wave's update slot beside two factor waves and beside one (kb_solve_layout.h), once for all panels
+  const int ow2 = kb_slay::upd_slot(7, 1, wave), ow1 = kb_slay::upd_slot(7, 2, wave);
+  static_assert(kb_slay::factor_waves(7, 1) == 2 && kb_slay::factor_waves(7, 2) == 1, "a panel of either kind");
+  KB_TS(d, 250);
 #pragma unroll 1
   for (int q = 0; q < nb; ++q) {
     if (q > 0) {
@@ -3625,7 +3633,10 @@ __device__ __forceinline__ void ldl_panels(const KbDev& d, double* S, double* rD
       }
       __syncthreads();
     }
-    const int nf = (nb - 1 - q) > 4 ? 2 : 1;  // 4 tiles below per factor wave
+    const int nf = (nb - 1 - q) > 4 ? 2 : 1;  // 4 tiles below per factor wave: kb_slay::factor_waves(nb, q)
+    const int ns = kb_slay::upd_slots(nb, q), ow = nf == 2 ? ow2 : ow1;
+    kb_slay::UpdItem a = kb_slay::upd_first(nb, q, ow);
+    if (q == 0) KB_TS(d, 251);
     if (wave < nf) {
       if (wave == 0) KB_TS(d, 20 + 2 * q);
       const bool ok = panel_factor2(d, S, rD, Dfac, q, nb, C, wave);
@@ -3634,31 +3645,42 @@ __device__ __forceinline__ void ldl_panels(const KbDev& d, double* S, double* rD
         KB_WAVE_SYNC();
         KB_TS(d, 21 + 2 * q);
       }
-    } else if (ow >= 0 && q > 0) {
-      // panel q-1 on tiles (q+1+ii, q+1+jj), 0 <= jj <= ii < m
-      const int m = nb - 1 - q, ntiles = m * (m + 1) / 2;
-      const double* rdq = rD + 16 * (q - 1);
-      // two tiles at a time: all their operands in one round of LDS loads, then 8 MFMAs in two chains
-      // (four tiles per round, one round for the 15 tiles of the first trailing update at C = 106, measured slower:
-      // panel 1 2.52 -> 2.76 us, tools/micro/camera_solve)
+    } else if (q > 0 && ow >= 0 && a.i < nb) {  // a slot with a tile (wave 5 has none at the last panel)
+      // earlier panels on column q+1 (and on the one tile brought forward): this slot's items (kb_solve_layout.h), two
+      // per round: all their operands and both tiles in one round of LDS loads, then 8 MFMAs in two chains.  A tile is
+      // read at its first item of the phase, takes its products one after another in registers, (T - P_p) - P_p+1 ...,
+      // and is stored at its last (p == q - 1)
+      const int r16 = lane & 15, kq = lane >> 4;
+      int pi = -1;  // the tile row of the item before (a slot's tiles differ in their rows)
+      double t[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 1
-      for (int qq = ow; qq < ntiles; qq += 8) {
-        const int qb = min(qq + 4, ntiles - 1);
-        const int ia = tri_row(qq), ja = qq - ia * (ia + 1) / 2, ib = tri_row(qb), jb = qb - ib * (ib + 1) / 2;
-        const double* Wia = S + tile_base(q + 1 + ia, q - 1);
-        const double* Wja = S + tile_base(q + 1 + ja, q - 1);
-        const double* Wib = S + tile_base(q + 1 + ib, q - 1);
-        const double* Wjb = S + tile_base(q + 1 + jb, q - 1);
-        const int r16 = lane & 15, kq = lane >> 4;
-        double aa[4], ba[4], ab[4], bb[4];
+      while (a.i < nb) {
+        const kb_slay::UpdItem bn = kb_slay::upd_next(a, nb, q, ns);
+        const bool hb = bn.i < nb;  // wave-uniform
+        const kb_slay::UpdItem b = hb ? bn : a;
+        const bool firsta = a.i != pi, firstb = b.i != a.i;
+        const double* Wia = S + tile_base(a.i, a.p);
+        const double* Wja = S + tile_base(a.j, a.p);
+        const double* Wib = S + tile_base(b.i, b.p);
+        const double* Wjb = S + tile_base(b.j, b.p);
+        const double* rda = rD + 16 * a.p;
+        const double* rdb = rD + 16 * b.p;
+        double* Ta = S + tile_base(a.i, a.j);
+        double* Tb = S + tile_base(b.i, b.j);
+        double aa[4], ba[4], ab[4], bb[4], ta[4], tb[4];
 #pragma unroll
         for (int st = 0; st < 4; ++st) {
           const int k = 4 * st + kq;
-          const double rk = rdq[k];
           aa[st] = Wia[r16 * kTS + k];
-          ba[st] = Wja[r16 * kTS + k] * rk;
+          ba[st] = Wja[r16 * kTS + k] * rda[k];
           ab[st] = Wib[r16 * kTS + k];
-          bb[st] = Wjb[r16 * kTS + k] * rk;
+          bb[st] = Wjb[r16 * kTS + k] * rdb[k];
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int e = (kq + 4 * r) * kTS + r16;
+          ta[r] = Ta[e];
+          tb[r] = Tb[e];
         }
         v4d acca = {0.0, 0.0, 0.0, 0.0}, accb = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -3666,13 +3688,24 @@ __device__ __forceinline__ void ldl_panels(const KbDev& d, double* S, double* rD
           acca = __builtin_amdgcn_mfma_f64_16x16x4f64(aa[st], ba[st], acca, 0, 0, 0);
           accb = __builtin_amdgcn_mfma_f64_16x16x4f64(ab[st], bb[st], accb, 0, 0, 0);
         }
-        double* Ta = S + tile_base(q + 1 + ia, q + 1 + ja);
-        tile_sub(Ta, Ta, acca, lane);
-        if (qq + 4 < ntiles) {  // wave-uniform
-          double* Tb = S + tile_base(q + 1 + ib, q + 1 + jb);
-          tile_sub(Tb, Tb, accb, lane);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) t[r] = (firsta ? ta[r] : t[r]) - acca[r];
+        if (a.p == q - 1) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) Ta[(kq + 4 * r) * kTS + r16] = t[r];
         }
+        if (hb) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) t[r] = (firstb ? tb[r] : t[r]) - accb[r];
+          if (b.p == q - 1) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Tb[(kq + 4 * r) * kTS + r16] = t[r];
+          }
+        }
+        pi = b.i;
+        a = hb ? kb_slay::upd_next(b, nb, q, ns) : bn;
       }
+      KB_TSW(d, 128 + 8 * q + wave);
     } else if ((wave == 1 || wave == 5) && q >= 2) {
       // the factored diagonal tiles' inverses for the backsolve on SIMD 1, idle once panel q has one factor wave
       // (q >= 2 for C <= 111): tile t at panel t + 2 on wave 1, the last one (t = nb - 2) at the last panel on wave 5;
@@ -4561,8 +4594,14 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
     KB_STAMP(d, 4);
   } else {
     // phase C: blocked LDL^T with the forward solve (row C); the previous pass's end beside the first panel
+    KB_TS(d, 247);
     if (gfu && fwave) finish_prev();
-    if (d.pcs_cb) {  // KB_SOLVER_PCG_SCHUR (per-call path): S and b = row C of the k_colimg image
+    KB_TS(d, 248);
+    // KB_SOLVER_PCG_SCHUR (per-call path): S and b = row C of the k_colimg image.  Marked unlikely so that its body
+    // lies behind the factorisation's code: wave 0 then falls through towards panel 0 instead of branching over the
+    // inlined schur_pcg (round 20: 0.44 us at that branch, 0.08 us without it; no instruction runs in between, so
+    // presumably a fetch of instructions that are not cached at that point of a launch)
+    if (__builtin_expect(d.pcs_cb != nullptr, 0)) {
       auto sget = [&](int i, int j) { return S[i >= j ? tidx(i, j) : tidx(j, i)]; };
       double* bcol = rDv;  // b (row C of the image) as a vector; rDv is unused without the LDL^T
       for (int j = tid; j < C; j += nth) bcol[j] = S[tidx(C, j)];
@@ -4571,6 +4610,7 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
       __syncthreads();
       if (tid < 64 && okl && !(gfu && fin[0])) wave0_tail(gfu ? fin[1] : cur);
     } else {
+    KB_TS(d, 249);
     ldl_panels(d, S, rDv, Dfac, Xinv, C, nb, &okl);  // ends with a block barrier: okl and fin are final
     KB_TS(d, 4);
     KB_STAMP(d, 3);
@@ -4606,7 +4646,10 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
         }
         KB_WAVE_SYNC();
       }
-      chain_pairs<true>(d, nbase, chl, lane);  // the K entries: all waves after the barrier (chain_write)
+      // the K entries: all waves after the barrier (chain_write).  Storing them from the idle waves beside the
+      // backsolve, behind an LDS flag, was measured slower: this wave ends after wave 0
+      chain_pairs<true>(d, nbase, chl, lane);
+      KB_TSW(d, 252);
     }
     }
     KB_STAMP(d, 4);

@@ -59,6 +59,36 @@ KB_SLAY_HD constexpr int img_ntz(int C) { return KB_SLAY_NTZ(nb(C)); }
 KB_SLAY_HD constexpr int img_n16(int C) { return 16 * nb(C); }
 KB_SLAY_HD constexpr int img_n(int C) { return img_ntz(C) + img_n16(C) + 2 + kXMaxRanks; }
 
+// ---- the trailing updates of the blocked LDL^T (ldl_panels, C > 64), left-looking: while panel q >= 1 is factored,
+// the update waves bring column q + 1 up to date with the panels 0 .. q - 1, so that phase A of panel q + 1 (panel q
+// on column q + 1) completes it.  An item is one tile product: panel p subtracted from tile (i, q + 1).  Update slot
+// ow of the phase's ns slots takes the tiles i = q + 1 + ow + ns u and walks each through p = 0 .. q - 1 before the
+// next, so a tile's products stay on one wave and arrive in panel order.  The slots are waves off the SIMDs that
+// factor: 2, 3, 6, 7 (SIMDs 2, 3) while panel q has two factor waves (waves 0 and 1: more than four tiles below it),
+// and wave 5 as well once wave 0 factors alone and SIMD 1 is free (three tiles then sit on three SIMDs).  ldl_panels
+// steps with upd_first / upd_next and takes two items per round; the CPU test walks the same functions
+KB_SLAY_HD constexpr int factor_waves(int nb, int q) { return nb - 1 - q > 4 ? 2 : 1; }  // four tiles below per wave
+KB_SLAY_HD constexpr int upd_slots(int nb, int q) { return factor_waves(nb, q) == 2 ? 4 : 5; }
+// the slot of block wave `wave` at panel q, or -1
+KB_SLAY_HD constexpr int upd_slot(int nb, int q, int wave) {
+  if (upd_slots(nb, q) == 4) return wave == 2 ? 0 : wave == 3 ? 1 : wave == 6 ? 2 : wave == 7 ? 3 : -1;
+  return wave == 2 ? 0 : wave == 3 ? 1 : wave == 5 ? 2 : wave == 6 ? 3 : wave == 7 ? 4 : -1;
+}
+// One tile is brought forward: the last diagonal tile (nb - 1, nb - 1) would take all its nb - 2 products on one wave
+// in phase B of panel nb - 2, longer than that panel's factor.  Slot 2, idle in phase B of panel nb - 3 (two tiles in
+// column nb - 2), applies the panels 0 .. nb - 4 to it there; phase B of panel nb - 2 adds panel nb - 3 alone.
+struct UpdItem {
+  int i, j, p;  // tile (i, j) (done: i >= nb) | panel
+};
+KB_SLAY_HD constexpr UpdItem upd_first(int nb, int q, int ow) {
+  if (q == nb - 3 && ow == 2) return {nb - 1, nb - 1, 0};
+  return {q + 1 + ow, q + 1, (q == nb - 2 && ow == 0) ? q - 1 : 0};
+}
+KB_SLAY_HD constexpr UpdItem upd_next(UpdItem a, int nb, int q, int ns) {
+  if (a.p + 1 < q) return {a.i, a.j, a.p + 1};
+  return a.j == q + 1 ? UpdItem{a.i + ns, a.j, 0} : UpdItem{nb, a.j, 0};
+}
+
 // ---- the dynamic LDS of solve_body<CM> (k_solve) and k_cov_cam<CM>
 //   packed (CM > 0): S column-major packed lower [C(C+1)/2] | bv [C + 1] (slot C: non-PD count) | gl [C] |
 //     Hs [N][256] | T [N][N][36] | K [N][N][36] | ci [C] ints

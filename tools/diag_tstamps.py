@@ -31,6 +31,17 @@ for t in range(7):
 for q in range(7):
     names[20 + 2 * q] = f"    p{q} factor start (after its MFMA lookahead)"
     names[21 + 2 * q] = f"    p{q} factor end"
+# lane 0 of other waves (KB_TSW): the update waves' last store of each panel's phase B, wave 1's pair products, the
+# chain-writing waves; and wave 0's way from the "H_cc blocks + grad" barrier to the first panel's factor
+for q in range(1, 7):
+    for w in (2, 3, 5, 6, 7):
+        names[128 + 8 * q + w] = f"    p{q}: update wave {w} done"
+names[252] = "  wave 1: pair products done"
+names[247] = "  w0: past the stop point"
+names[248] = "  w0: past finish_prev's branch"
+names[249] = "  w0: past the pcs_cb branch"
+names[250] = "  w0: ldl_panels entry"
+names[251] = "  w0: panel 0, before the factor branch"
 for rep in range(3):
     g.set_state(p.state_init)
     g.run_gn(16)
