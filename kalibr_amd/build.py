@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "kb_capi.hip")
 SRC_SPLINE = os.path.join(HERE, "csrc", "kb_spline.hip")
 OUT = os.path.join(HERE, "libkalibr_hip.so")
-DEPS = ["kb_capi.hip", "kb_kernels.hip", "kb_pcg.hip", "kb_dogleg.hip", "kb_robust.hip", "kb_device.h", "kb_math.h", "kb_build_layout.h", "kb_solve_layout.h", "kb_syrk_tile.h", "kb_spline.hip", "kb_spline_dogleg.hip", "kb_build_tu.hip"]
+DEPS = ["kb_capi.hip", "kb_kernels.hip", "kb_pcg.hip", "kb_dogleg.hip", "kb_robust.hip", "kb_device.h", "kb_policy.h", "kb_math.h", "kb_build_layout.h", "kb_solve_layout.h", "kb_syrk_tile.h", "kb_spline.hip", "kb_spline_dogleg.hip", "kb_build_tu.hip"]
 SRC_BUILD_TU = os.path.join(HERE, "csrc", "kb_build_tu.hip")
 N_BUILD_TU = 9  # camera-model sets, one translation unit each (kb_build_tu.hip -DKB_TU_ID=i)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -2309,7 +2309,7 @@ int kb_set_dogleg_options(kb_handle* h, const kb_dogleg_options* opts) {
   if (!h) return fail("kb_set_dogleg_options: null");
   const kb_dogleg_options def{0.0};
   const kb_dogleg_options o = opts ? *opts : def;
-  if (!(o.delta_init >= 0.0) || !std::isfinite(o.delta_init))
+  if (!dl_delta_valid(o.delta_init))
     return fail("kb_set_dogleg_options: delta_init must be finite and >= 0");
   h->dl_opts = o;
   return 0;
@@ -2322,14 +2322,13 @@ int kb_dogleg_step(kb_handle* h, double delta, double* dx_out, kb_dogleg_info* i
   if (!h->sys_valid) return fail("kb_dogleg_step: no intact system (call kb_build first; the optimizer loops do "
                                  "not leave the per-call blocks)");
   if (sharded(h)) return fail("kb_dogleg_step: per-call quantity of an unsharded handle");
-  if (!(delta >= 0.0) || !std::isfinite(delta)) return fail("kb_dogleg_step: delta must be finite and >= 0");
+  if (!dl_delta_valid(delta)) return fail("kb_dogleg_step: delta must be finite and >= 0");
   KB_HIP(hipSetDevice(h->device));
   unprepare(h);
   if (ensure_dl(h, 0)) return -1;
   const KbDlBuf b = h->dl;
-  KbDl st{};
-  st.delta = delta;
-  st.step_type = -1;
+  KbDl st;
+  dl_start(&st, delta);
   KB_HIP(hipMemcpyAsync(b.s, &st, sizeof(KbDl), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_dl_sd_frames, dim3((h->F + h->C + 3) / 4), dim3(256), 0, h->stream, h->d, b, 0);
   hipLaunchKernelGGL(k_dl_sd_final, dim3(1), dim3(256), 0, h->stream, h->d, b, 0);

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "kb_math.h"
+#include "kb_policy.h"  // KbCtrl, KbOpts, KbDl and the policy arithmetic over them
 #include "kb_solve_layout.h"
 
 namespace kb {
@@ -24,22 +25,6 @@ namespace kb {
 // the reduced-system launch layout: limits, selectors, LDS maps and k_marg's sizes (kTS, kTileSz, kXMaxRanks, kCovWaves,
 // kCovMaxC, kMargMaxC, kMargThreads, kMargLdsStage, nb, solve_map, marg_threads, marg_block, ...)
 using namespace kb_slay;
-
-struct KbCtrl {
-  int cur, done, do_build, solve_ok, first, prev_failed, lin_fail;
-  int iterations, failed_iterations, max_iterations, policy, n_trace, passes;
-  int pending;  // a pass ran its solve: its accept/revert + the next prelude are still to apply
-  int have_dx;  // GN fused passes: the last solve's dx is still to apply (by the next build or the finish)
-  int comm_err;  // k_xar: a peer rank did not arrive within the wait bound (the pass batch ends, the host fails the call)
-  double J, p_J, J_start, deltaX, deltaJ, eps_x, eps_j;
-  double pol_J, pol_pJ, last_succ, lambda, mu;
-  double dxdx, dxrhs;
-};
-
-struct KbOpts {
-  int policy, max_iterations;
-  double lambda_init, eps_x, eps_j;
-};
 
 constexpr int kColsumRows = 8;  // stage-1 row splits of the block partial reduction
 constexpr int kXarBlocks = 32;        // k_xar blocks (each sums one chunk of the image over the ranks)

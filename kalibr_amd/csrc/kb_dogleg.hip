@@ -1,20 +1,13 @@
 // kb_dogleg.hip -- the dog-leg trust-region policy on the device, FP64 throughout.
 //
-// Restates aslam_backend's DogLegTrustRegionPolicy (aslam_optimizer/aslam_backend/src/DogLegTrustRegionPolicy.cpp:
-// 11-161, driven by Optimizer2.cpp:183-273 and TrustRegionPolicy.cpp:29-52) statement by statement over the arrow
-// system the build kernels leave (H_ff, H_fc, g_f per frame; H_cc, g_c):
-//   prelude     rho = get_dJ() / L0, trust-radius update (:33-59), rebuild only after an accepted step (:63-79)
-//   SD          sd_scale = g.g / g^T (J^T J) g, dx_sd = sd_scale g (:70-75)
-//   selection   SD (:82-87) | GN (:109-114) | DL with beta of :118-131 (:115-136); the GN step is solved only when
-//               the SD branch is not taken (:92-102)
-// dx_sd is never materialised: with s = sd_scale, gg = g.g, n = dx_gn.dx_gn, p = g.dx_gn
-//   |dx_sd|^2 = s^2 gg,  c = dx_sd.(dx_gn - dx_sd) = s p - s^2 gg,  |dx_gn - dx_sd|^2 = n - 2 s p + s^2 gg
-// and every step is dx = a g + b dx_gn: SD (delta / |dx_sd| s, 0), GN (0, 1), DL ((1 - beta) s, beta).
-//
-// Deviations from the reference (also in include/kalibr_hip.h):
-//   1. delta_init: optimizationStarting assigns it to delta (the reference: 0, the default here).
-//   2. the GN step counts as held only after a completed solve (the reference sets gnComputed before it knows);
-//      a failed solve is a failed iteration and is retried on the next pass.
+// The policy itself (aslam_backend's DogLegTrustRegionPolicy.cpp:11-161, driven by Optimizer2.cpp:183-273 and
+// TrustRegionPolicy.cpp:29-52, its algebra without dx_sd and the two deviations from the reference) is kb_policy.h's:
+// KbDl and dl_start, dl_set_sd, dl_sd_branch, dl_hold_gn, dl_select, dl_radius.  Here are the kernels that feed it over
+// the arrow system the build kernels leave (H_ff, H_fc, g_f per frame; H_cc, g_c):
+//   SD          the reduction of g.g and g^T (J^T J) g, then whether the pass needs the GN solve (solved only when the
+//               SD branch is not taken, :92-102)
+//   selection   the dot products of a fresh GN step, then dl_select; dx = a g + b dx_gn, update, chains, cost
+//   pass end    accept / revert, trace, the next pass's prelude and radius update; rebuild only after an accepted step
 //
 // Every reduction has a fixed order (per-frame or per-block partials, then one block sums them in index order);
 // no floating-point atomics.  The dog-leg state lives in KbDl, not in KbCtrl (the hot kernels copy KbCtrl whole).
@@ -24,20 +17,6 @@
 #include "kb_device.h"
 
 namespace kb {
-
-struct KbDl {
-  double delta, p_delta, delta_init;
-  double sd_scale, dx_sd_norm, dx_gn_norm, beta, L0;
-  double gg, ghg;   // g.g and g^T (J^T J) g of the held system
-  double gn2, ggn;  // dx_gn.dx_gn and g.dx_gn of the held GN step
-  double dx_norm;   // |dx| of the last step (the 3 |dx| rule, :41)
-  double a, b;      // dx = a g + b dx_gn
-  double J;         // the cost L0 was formed with (per-call query: the build's chi^2)
-  int step_type;    // 0 SD, 1 GN, 2 DL (of the last completed selection)
-  int gn_held;      // dx_gn is the GN step of the held system
-  int need_gn;      // this pass solves for it
-  int step_ok;      // this pass has a step (0: the solve it needed failed)
-};
 
 struct KbDlBuf {
   KbDl* s;
@@ -52,8 +31,6 @@ struct KbDlBuf {
   int trace_cap;    // rows of trace
 };
 
-constexpr int kDlTrace = 6;
-
 // sum of one value per thread over a 256-thread block, fixed order (wave sums, then the four waves in order)
 __device__ __forceinline__ double dl_block_sum(double v, double* sh4) {
   v = wave_sum_d(v);
@@ -65,11 +42,7 @@ __device__ __forceinline__ double dl_block_sum(double v, double* sh4) {
 
 // optimizationStartingImplementation (:11-22) after the loop start's generic prelude; delta = delta_init (deviation 1)
 __global__ void k_dl_init(KbDev d, KbDlBuf b, double delta_init) {
-  KbDl s{};
-  s.delta = delta_init;
-  s.delta_init = delta_init;
-  s.step_type = -1;
-  *b.s = s;
+  dl_start(b.s, delta_init);
   *b.gb = *d.ctrl;
   b.gb->done = b.gb->done || !b.gb->do_build;
 }
@@ -138,19 +111,10 @@ __global__ void __launch_bounds__(256) k_dl_sd_final(KbDev d, KbDlBuf b, int gat
     }
     h = dl_block_sum(h, sh);
     g = dl_block_sum(g, sh);
-    if (tid == 0) {
-      s->gg = g;
-      s->ghg = h;
-      s->sd_scale = g / h;
-      s->dx_sd_norm = fabs(s->sd_scale) * sqrt(g);
-      s->gn_held = 0;  // "invalidate GN solution" (:78)
-      s->gn2 = s->ggn = s->dx_gn_norm = 0.0;
-    }
+    if (tid == 0) dl_set_sd(s, g, h);
   }
   if (tid == 0) {
-    const double delta = s->delta;
-    const bool sd = s->dx_sd_norm >= delta && delta != 0;
-    const int need = !sd && !s->gn_held;
+    const int need = !dl_sd_branch(s) && !s->gn_held;
     s->need_gn = need;
     if (gate) {
       *b.gs = *d.ctrl;
@@ -186,62 +150,8 @@ __global__ void __launch_bounds__(256) k_dl_select(KbDev d, KbDlBuf b, int gate)
     gp = dl_block_sum(gp, sh);
   }
   if (tid != 0) return;
-  if (need) {
-    s->gn2 = n2 + d.camstat[1];
-    s->ggn = gp + d.camstat[2];
-    s->dx_gn_norm = sqrt(s->gn2);
-    s->gn_held = 1;
-  }
-  const double J = gate ? cin.J : d.cost_build[0];
-  const double sc = s->sd_scale, sdn = s->dx_sd_norm, gg = s->gg;
-  double delta = s->delta;
-  int type;
-  double a, bb, L0, dxn;
-  if (sdn >= delta && delta != 0) {  // trust region smaller than SD: the scaled SD step
-    a = delta / sdn * sc;
-    bb = 0.0;
-    L0 = delta * (2 * sdn - delta) / (2 * sc);
-    dxn = delta;
-    type = 0;
-  } else {
-    const double gn2 = s->gn2, ggn = s->ggn, gnn = s->dx_gn_norm;
-    // "set delta in the first step": |dx_sd + (dx_gn - dx_sd) / 2| (:105-107)
-    if (delta == 0) delta = 0.5 * sqrt(sc * sc * gg + 2 * sc * ggn + gn2);
-    if (gnn <= delta) {
-      a = 0.0;
-      bb = 1.0;
-      L0 = J;
-      dxn = gnn;
-      type = 1;
-    } else {
-      const double dn2 = gn2 - 2 * sc * ggn + sc * sc * gg;  // |dx_gn - dx_sd|^2
-      const double c = sc * ggn - sc * sc * gg;               // dx_sd.(dx_gn - dx_sd)
-      const double r = delta * delta - sdn * sdn;
-      double beta;
-      if (c <= 0) {
-        beta = -c + sqrt(c * c + dn2 * r);
-        beta /= dn2;
-      } else {
-        beta = r;
-        beta /= c + sqrt(c * c + dn2 * r);
-      }
-      s->beta = beta;
-      a = (1 - beta) * sc;
-      bb = beta;
-      // the reference's first term carries the integer expression 1/2, which is 0 (:134): kept at 0
-      L0 = beta * (2 - beta) * J;
-      dxn = sqrt(a * a * gg + 2 * a * bb * ggn + bb * bb * gn2);
-      type = 2;
-    }
-  }
-  s->delta = delta;
-  s->a = a;
-  s->b = bb;
-  s->L0 = L0;
-  s->J = J;
-  s->dx_norm = dxn;
-  s->step_type = type;
-  s->step_ok = 1;
+  if (need) dl_hold_gn(s, n2 + d.camstat[1], gp + d.camstat[2]);
+  dl_select(s, gate ? cin.J : d.cost_build[0]);
 }
 
 // dx = a g + b dx_gn over the C + 6F columns into the buffer the update reads; per-block max |dx|
@@ -302,34 +212,14 @@ __global__ void __launch_bounds__(256) k_dl_policy(KbDev d, KbDlBuf b) {
   }
   if (tid != 0) return;
   KbCtrl cl = cin;
-  int accepted = 0;
-  if (!ok) {
-    cl.prev_failed = 1;
-    cl.lin_fail = 1;
-    cl.failed_iterations++;
-    J = NAN;
-    dX = cl.deltaX;
-  } else {
-    cl.deltaX = dX;
-    cl.J = J;
-    cl.deltaJ = cl.p_J - J;
-    if (cl.deltaJ < 0.0) {  // revertOnFailure(): state[cur] untouched, J stays at the rejected candidate's cost
-      cl.failed_iterations++;
-      cl.prev_failed = 1;
-    } else {
-      cl.cur = 1 - cl.cur;
-      cl.p_J = J;
-      cl.prev_failed = 0;
-      accepted = 1;
-    }
-    cl.iterations++;
-  }
+  const double red[4] = {J, 0.0, 0.0, dX};
+  const KbPassEnd e = pol_accept<true>(&cl, ok, red);
   if (cl.n_trace < d.trace_cap && cl.n_trace < b.trace_cap) {
     double* tr = d.trace + 4 * cl.n_trace;
-    tr[0] = J;
+    tr[0] = e.J;
     tr[1] = s->delta;  // the lambda column carries delta
-    tr[2] = dX;
-    tr[3] = accepted;
+    tr[2] = e.dX;
+    tr[3] = e.accepted;
     double* t = b.trace + kDlTrace * cl.n_trace;
     t[0] = s->delta;
     t[1] = ok ? s->step_type : -1;
@@ -342,21 +232,7 @@ __global__ void __launch_bounds__(256) k_dl_policy(KbDev d, KbDlBuf b) {
   cl.passes++;
   pol_pre<true>(&cl);  // while-condition and the base class's J bookkeeping (pol_J, pol_pJ)
   if (!cl.done) {
-    const double rho = (cl.pol_pJ - cl.pol_J) / s->L0;  // get_dJ() / _L0
-    double delta = s->delta;
-    s->p_delta = delta;
-    if (rho > 0.75) {  // step succeeded
-      const double n3 = 3 * s->dx_norm;
-      if (!(delta > n3)) delta = n3;
-    } else if (rho > 0 && rho < 0.25) {  // step almost failed
-      delta /= 2.0;
-    } else if (rho <= 0) {  // step failed
-      if (s->step_type == 1)
-        delta = s->dx_gn_norm / 2.0;
-      else
-        delta /= 2.0;
-    }
-    s->delta = delta;
+    dl_radius(s, (cl.pol_pJ - cl.pol_J) / s->L0);  // get_dJ() / _L0
     cl.do_build = !cl.prev_failed;
   }
   cl.pending = 0;

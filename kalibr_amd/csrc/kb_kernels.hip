@@ -222,98 +222,18 @@ __device__ __forceinline__ double chain_entry_reg(const double (&R)[9], const do
 }
 
 // ---------------------------------------------------------------------------------------------
-// policy: while-condition (Optimizer2.cpp:215-219) + TrustRegionPolicy::solveSystem prelude
-// (TrustRegionPolicy.cpp:39-52) + LM lambda schedule (LevenbergMarquardtTrustRegionPolicy.cpp:50-84)
-// or GN (build every pass, no conditioner: GaussNewtonTrustRegionPolicy.cpp:25-29).
+// policy: pol_pre (loop condition, J bookkeeping, LM / GN schedule) and pol_accept (accept / revert) are kb_policy.h's;
+// the pass end's trace row is written here.  red = [cost, dx.dx, dx.rhs, max|dx|] (all ranks)
 // ---------------------------------------------------------------------------------------------
-template <bool GN_ONLY = false>
-__device__ __forceinline__ void pol_pre(KbCtrl* c) {
-  const bool cont = c->iterations < c->max_iterations && c->failed_iterations < c->max_iterations &&
-                    ((c->deltaX > c->eps_x && fabs(c->deltaJ) > c->eps_j) || c->lin_fail);
-  if (!cont) {
-    c->done = 1;
-    return;
-  }
-  const double J = c->J;
-  if (c->prev_failed) {
-    c->pol_J = J;
-  } else {
-    c->pol_pJ = c->last_succ;
-    c->last_succ = J;
-    c->pol_J = J;
-  }
-  c->solve_ok = 1;
-  if (!GN_ONLY && c->policy == 0) {
-    if (c->first) {
-      c->do_build = 1;
-    } else {
-      const double d2 = c->lambda * c->dxdx + c->dxrhs;  // dx^T (lambda dx + rhs), getLmRho (:107-113)
-      const double rho = (c->pol_pJ - c->pol_J) / d2;
-      if (c->prev_failed) {
-        c->mu *= 2;
-        c->lambda *= c->mu;
-        c->do_build = 0;
-      } else if (rho <= 0) {
-        c->mu *= 10;
-        c->lambda *= c->mu;
-        c->do_build = 0;
-      } else {
-        c->do_build = 1;
-        if (c->lambda > 1e-16) {
-          const double gamma = 3.0, beta = 2.0;
-          const double u1 = 1 / gamma;
-          const double u2 = 1 - (beta - 1) * pow((2 * rho - 1), 3.0);
-          if (u1 > u2)
-            c->lambda *= u1;
-          else
-            c->lambda *= u2;
-          c->mu = beta;
-        } else {
-          c->lambda = 1e-15;
-        }
-      }
-    }
-  } else {
-    c->do_build = 1;
-  }
-  c->first = 0;
-}
-
-// accept / revert (Optimizer2.cpp:221-259); red = [cost, dx.dx, dx.rhs, max|dx|] (all ranks)
 __device__ __forceinline__ void pol_post(KbCtrl* c, const KbDev& d, const double* red, bool write_trace = true) {
-  double J = 0.0, dX = c->deltaX;
-  int accepted = 0;
-  if (!c->solve_ok) {
-    c->prev_failed = 1;
-    c->lin_fail = 1;
-    c->failed_iterations++;
-    J = NAN;
-  } else {
-    J = red[0];
-    dX = red[3];
-    c->dxdx = red[1];
-    c->dxrhs = red[2];
-    c->deltaX = dX;
-    c->J = J;
-    c->deltaJ = c->p_J - J;
-    if (c->policy == 0 && c->deltaJ < 0.0) {  // regression: revertLastStateUpdate (state[cur] untouched)
-      c->failed_iterations++;
-      c->prev_failed = 1;
-    } else {
-      c->cur = 1 - c->cur;
-      c->p_J = J;
-      c->prev_failed = 0;
-      accepted = 1;
-    }
-    c->iterations++;
-  }
+  const KbPassEnd e = pol_accept(c, c->solve_ok, red);
   if (c->n_trace < d.trace_cap) {
     double* tr = d.trace + 4 * c->n_trace;
     if (write_trace) {
-    tr[0] = J;
-    tr[1] = c->lambda;
-    tr[2] = dX;
-    tr[3] = accepted;
+      tr[0] = e.J;
+      tr[1] = c->lambda;
+      tr[2] = e.dX;
+      tr[3] = e.accepted;
     }
     c->n_trace++;
   }
@@ -5486,40 +5406,7 @@ __global__ void k_policy(KbDev d) {
   *c = cl;
 }
 
-__global__ void k_pol_init(KbDev d, KbOpts o) {
-  KbCtrl* c = d.ctrl;
-  const double J = d.red[0];
-  c->J = J;
-  c->p_J = J;
-  c->J_start = J;
-  c->deltaX = o.eps_x + 1.0;
-  c->deltaJ = o.eps_j + 1.0;
-  c->prev_failed = 0;
-  c->lin_fail = 0;
-  c->iterations = 0;
-  c->failed_iterations = 0;
-  c->max_iterations = o.max_iterations;
-  c->eps_x = o.eps_x;
-  c->eps_j = o.eps_j;
-  c->policy = o.policy;
-  // TrustRegionPolicy::optimizationStarting (TrustRegionPolicy.cpp:30-37), LM (:38-46)
-  c->pol_J = J;
-  c->pol_pJ = J;
-  c->last_succ = J;
-  c->first = 1;
-  c->lambda = o.policy == 0 ? o.lambda_init : 0.0;
-  c->mu = 2.0;
-  c->dxdx = 0.0;
-  c->dxrhs = 0.0;
-  c->done = 0;
-  c->do_build = 0;
-  c->solve_ok = 1;
-  c->n_trace = 0;
-  c->passes = 0;
-  c->pending = 0;
-  c->have_dx = 0;
-  c->comm_err = 0;  // (the host agreed on the transport at the loop start: a failed direct path is off by now)
-}
+__global__ void k_pol_init(KbDev d, KbOpts o) { pol_start(d.ctrl, o, d.red[0]); }
 
 // per-call update (kb_apply_update): all DVs from state[cur] -> state[1-cur]
 __device__ __forceinline__ void update_all_thread(const KbDev& d) {

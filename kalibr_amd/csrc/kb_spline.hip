@@ -27,6 +27,7 @@
 
 #include "../../include/kalibr_hip.h"
 #include "kb_math.h"
+#include "kb_policy.h"
 
 // diagnostic build only (KB_STAMPS, tools/gpu_sp_stops.sh): the timed kernels return after phase i when
 // KSP_DBG_STOP = i; the product library never reads the variable and has no early returns
@@ -4508,6 +4509,20 @@ int kb_sp_get_system(kb_sp_handle* h, double* Hcc, double* Hsc, double* Hband, d
 
 }  // extern "C"
 
+namespace {
+// what kb_sp_optimize reports of a finished loop, from the loop's control block (kb_policy.h)
+void sp_fill_solution(const kb::KbCtrl& c, kb_solution* out) {
+  out->J_start = c.J_start;
+  out->J_final = c.p_J;
+  out->dx_final = c.deltaX;
+  out->dj_final = c.deltaJ;
+  out->iterations = c.iterations;
+  out->failed_iterations = c.failed_iterations;
+  out->passes = c.passes;
+  out->linear_solver_failure = c.lin_fail;
+}
+}  // namespace
+
 // the dog-leg policy's host side: sp_dl_optimize (kb_sp_optimize policy 2) and the kb_sp_*dogleg* / kb_sp_rhs_jtj_rhs entries
 #define KSP_DL_HOST
 #include "kb_spline_dogleg.hip"
@@ -4648,93 +4663,43 @@ int kb_sp_optimize(kb_sp_handle* h, const kb_optimizer_options* o, kb_solution* 
   h->trace.clear();
   h->dl_trace.clear();
   if (o->policy == 2) return sp_dl_optimize(h, o, out);  // DogLeg (kb_spline_dogleg.hip)
-  const bool lm = o->policy == 0;
   const int ncols = h->ncols;
   std::vector<double> dx(ncols, 0.0), rhs(ncols, 0.0), tmp(ncols);
   double J;
   if (kb_sp_eval_cost(h, &J)) return -1;
-  double p_J = J;
-  out->J_start = p_J;
-  double deltaX = o->convergence_dx + 1.0, deltaJ = o->convergence_dj + 1.0;
-  bool prevFailed = false, linFail = false, first = true;
-  double pol_J = J, pol_pJ = J, last_succ = J;
-  double lambda = o->lambda_init, gamma = 3.0, beta = 2.0, mu = 2.0;
-  while (out->iterations < o->max_iterations && out->failed_iterations < o->max_iterations &&
-         ((deltaX > o->convergence_dx && std::fabs(deltaJ) > o->convergence_dj) || linFail)) {
-    if (prevFailed) {
-      pol_J = J;
-    } else {
-      pol_pJ = last_succ;
-      last_succ = J;
-      pol_J = J;
-    }
-    bool rebuild = true;
-    if (lm && !first) {
-      double d2 = 0.0;
-      for (int q = 0; q < ncols; ++q) d2 += dx[q] * (lambda * dx[q] + rhs[q]);
-      const double rho = (pol_pJ - pol_J) / d2;
-      if (prevFailed) {
-        mu *= 2;
-        lambda *= mu;
-        rebuild = false;
-      } else if (rho <= 0) {
-        mu *= 10;
-        lambda *= mu;
-        rebuild = false;
-      } else if (lambda > 1e-16) {
-        const double u1 = 1 / gamma, u2 = 1 - (beta - 1) * std::pow((2 * rho - 1), 3);
-        lambda *= (u1 > u2) ? u1 : u2;
-        mu = beta;
-      } else {
-        lambda = 1e-15;
-      }
-    }
-    if (rebuild) {
+  kb::KbCtrl c{};
+  kb::pol_start(&c, kb::KbOpts{o->policy, o->max_iterations, o->lambda_init, o->convergence_dx, o->convergence_dj}, J);
+  // getLmRho's denominator from the last step and the right-hand side it was solved from, one sum over the columns
+  const auto d2 = [&] {
+    double v = 0.0;
+    for (int q = 0; q < ncols; ++q) v += dx[q] * (c.lambda * dx[q] + rhs[q]);
+    return v;
+  };
+  for (kb::pol_pre(&c, d2); !c.done; kb::pol_pre(&c, d2)) {
+    if (c.do_build) {
       if (kb_sp_build(h)) return -1;
       if (kb_sp_get_rhs(h, rhs.data())) return -1;
     } else {
       h->built = true;  // same system, new conditioner
     }
-    h->lambda = lm ? lambda : 0.0;
+    h->lambda = c.lambda;
     int ok = 0;
     if (kb_sp_solve(h, tmp.data(), &ok)) return -1;
-    if (ok) dx = tmp;
-    first = false;
-    int accepted = 0;
-    if (!ok) {
-      prevFailed = true;
-      linFail = true;
-      out->failed_iterations++;
-    } else {
-      if (kb_sp_apply_update(h, nullptr, &deltaX)) return -1;
-      if (kb_sp_eval_cost(h, &J)) return -1;
-      deltaJ = p_J - J;
-      if (lm) {
-        if (deltaJ < 0.0) {
-          if (kb_sp_revert(h)) return -1;
-          out->failed_iterations++;
-          prevFailed = true;
-        } else {
-          p_J = J;
-          prevFailed = false;
-          accepted = 1;
-        }
-      } else {
-        p_J = J;
-        accepted = 1;
-      }
-      out->iterations++;
+    double red[4] = {0.0, 0.0, 0.0, 0.0};  // cost and max |dx| of the candidate (the step sums stay on the host: d2)
+    if (ok) {
+      dx = tmp;
+      if (kb_sp_apply_update(h, nullptr, &red[3])) return -1;
+      if (kb_sp_eval_cost(h, &red[0])) return -1;
     }
-    h->trace.push_back(ok ? J : NAN);
-    h->trace.push_back(lm ? lambda : 0.0);
-    h->trace.push_back(deltaX);
-    h->trace.push_back(accepted);
-    out->passes++;
+    const kb::KbPassEnd e = kb::pol_accept(&c, ok != 0, red);
+    if (ok && !e.accepted && kb_sp_revert(h)) return -1;
+    h->trace.push_back(e.J);
+    h->trace.push_back(c.lambda);
+    h->trace.push_back(e.dX);
+    h->trace.push_back(e.accepted);
+    c.passes++;
   }
-  out->J_final = p_J;
-  out->dx_final = deltaX;
-  out->dj_final = deltaJ;
-  out->linear_solver_failure = linFail;
+  sp_fill_solution(c, out);
   return 0;
 }
 

@@ -2,15 +2,12 @@
 // Included twice by kb_spline.hip (one translation unit: the kernels read SpDev, the host side the handle and its launch
 // helpers): with KSP_DL_DEVICE after the path's kernels, with KSP_DL_HOST after its per-call entry points.
 //
-// The policy is kb_dogleg.hip's (aslam_backend DogLegTrustRegionPolicy.cpp:11-161 inside Optimizer2.cpp:183-273, with
-// the project's two deviations: delta_init, and a GN step that counts as held only after a completed solve), and so is
-// the algebra: with s = sd_scale, gg = g.g, n = dx_gn.dx_gn, p = g.dx_gn
-//   |dx_sd|^2 = s^2 gg,  c = dx_sd.(dx_gn - dx_sd) = s p - s^2 gg,  |dx_gn - dx_sd|^2 = n - 2 s p + s^2 gg
-// and every step is dx = a g + b dx_gn: SD (delta / |dx_sd| s, 0), GN (0, 1), DL ((1 - beta) s, beta); dx_sd is never
-// materialised.  Unlike the camera path's device-resident loop, the loop is driven by the host like this path's LM and
-// GN loops: the kernels reduce over the blocks k_sp_assemble / k_sp_reduce_cc left in HBM
+// The policy (aslam_backend DogLegTrustRegionPolicy.cpp:11-161 inside Optimizer2.cpp:183-273, the project's two deviations
+// and the algebra that never materialises dx_sd: every step is dx = a g + b dx_gn) is kb_policy.h's, the functions the
+// camera path's device-resident loop calls.  Here the loop is driven by the host like this path's LM and GN loops: the
+// kernels reduce over the blocks k_sp_assemble / k_sp_reduce_cc left in HBM
 //   g = [g_theta | g_s]: Hcc[C C ..) and column C of R0;  H: Hcc, R0[:, :C], D0, U0 (no conditioner, lambda^2 never added)
-// and leave four scalars beside the SC_* ones; the policy arithmetic runs on the host in double, and nothing but the
+// and leave four scalars beside the SC_* ones; the policy runs on the host over a KbCtrl and a KbDl, and nothing but the
 // scalar block crosses PCIe inside the loop.  No floating-point atomics; every sum has a fixed order (per-node or
 // per-block partials in HBM, then one block over them in index order), so two runs from one state agree bitwise.
 
@@ -227,8 +224,6 @@ __global__ void __launch_bounds__(64) k_sp_dl_step(SpDev d, SpDl b, double* out,
 // host side
 // ==================================================================================================
 namespace {
-constexpr int kSpDlTrace = 6;
-
 // the buffers of the policy, made by the first call that needs them
 int sp_dl_ensure(kb_sp_handle* h) {
   if (h->dl_ready) return 0;
@@ -262,169 +257,68 @@ int sp_dl_launch_gn(kb_sp_handle* h) {
   return 0;
 }
 
-// the policy's state on the host (kb_dogleg.hip's KbDl)
-struct SpDlState {
-  double delta = 0.0, sd_scale = 0.0, dx_sd_norm = 0.0, dx_gn_norm = 0.0, beta = 0.0, L0 = 0.0;
-  double gg = 0.0, ghg = 0.0, gn2 = 0.0, ggn = 0.0, dx_norm = 0.0, a = 0.0, b = 0.0;
-  int step_type = -1;
-  bool gn_held = false;
-};
-
-// :70-75 from the two sums, and "invalidate GN solution" (:78)
-void sp_dl_set_sd(SpDlState& s, double gg, double ghg) {
-  s.gg = gg;
-  s.ghg = ghg;
-  s.sd_scale = gg / ghg;
-  s.dx_sd_norm = std::fabs(s.sd_scale) * std::sqrt(gg);
-  s.gn_held = false;
-  s.gn2 = s.ggn = s.dx_gn_norm = 0.0;
-}
-
-bool sp_dl_sd_branch(const SpDlState& s) { return s.dx_sd_norm >= s.delta && s.delta != 0; }
-
-// the selection (:82-137), k_dl_select's arithmetic; J is the cost L0 is formed with
-void sp_dl_select(SpDlState& s, double J) {
-  const double sc = s.sd_scale, sdn = s.dx_sd_norm, gg = s.gg;
-  double delta = s.delta;
-  if (sdn >= delta && delta != 0) {  // trust region smaller than SD: the scaled SD step
-    s.a = delta / sdn * sc;
-    s.b = 0.0;
-    s.L0 = delta * (2 * sdn - delta) / (2 * sc);
-    s.dx_norm = delta;
-    s.step_type = 0;
-  } else {
-    const double gn2 = s.gn2, ggn = s.ggn, gnn = s.dx_gn_norm;
-    // "set delta in the first step": |dx_sd + (dx_gn - dx_sd) / 2| (:105-107)
-    if (delta == 0) delta = 0.5 * std::sqrt(sc * sc * gg + 2 * sc * ggn + gn2);
-    if (gnn <= delta) {
-      s.a = 0.0;
-      s.b = 1.0;
-      s.L0 = J;
-      s.dx_norm = gnn;
-      s.step_type = 1;
-    } else {
-      const double dn2 = gn2 - 2 * sc * ggn + sc * sc * gg;  // |dx_gn - dx_sd|^2
-      const double c = sc * ggn - sc * sc * gg;               // dx_sd.(dx_gn - dx_sd)
-      const double r = delta * delta - sdn * sdn;
-      double beta;
-      if (c <= 0) {
-        beta = -c + std::sqrt(c * c + dn2 * r);
-        beta /= dn2;
-      } else {
-        beta = r;
-        beta /= c + std::sqrt(c * c + dn2 * r);
-      }
-      s.beta = beta;
-      s.a = (1 - beta) * sc;
-      s.b = beta;
-      // the reference's first term carries the integer expression 1/2, which is 0 (:134): kept at 0
-      s.L0 = beta * (2 - beta) * J;
-      s.dx_norm = std::sqrt(s.a * s.a * gg + 2 * s.a * s.b * ggn + s.b * s.b * gn2);
-      s.step_type = 2;
-    }
-  }
-  s.delta = delta;
-}
-
 // kb_sp_optimize, policy 2.  Per pass: [build, SD reduction, read-back] only after an accepted step; [GN solve, step
 // dots, read-back] only when the SD branch is not taken and no GN step of this system is held; step + update + cost,
-// read-back.  A pass after a rejected step launches the step, the update and the cost kernels alone.
+// read-back.  A pass after a rejected step launches the step, the update and the cost kernels alone.  The pass end and
+// the next pass's prelude are k_dl_policy's statements (kb_dogleg.hip) on the host.
 int sp_dl_optimize(kb_sp_handle* h, const kb_optimizer_options* o, kb_solution* out) {
   KSP_HIP(hipSetDevice(h->device));
   if (sp_dl_ensure(h)) return -1;
   SpDev& d = h->d;
   double J;
   if (kb_sp_eval_cost(h, &J)) return -1;
-  double p_J = J;
-  out->J_start = p_J;
-  double deltaX = o->convergence_dx + 1.0, deltaJ = o->convergence_dj + 1.0;
-  bool prevFailed = false, linFail = false, first = true;
-  double pol_J = J, pol_pJ = J, last_succ = J;
-  SpDlState s;
-  s.delta = h->dl_opts.delta_init;
+  kb::KbCtrl c{};
+  kb::pol_start(&c, kb::KbOpts{2, o->max_iterations, 0.0, o->convergence_dx, o->convergence_dj}, J);
+  kb::KbDl s;
+  kb::dl_start(&s, h->dl_opts.delta_init);
   h->dl_pass_ms.clear();
-  while (out->iterations < o->max_iterations && out->failed_iterations < o->max_iterations &&
-         ((deltaX > o->convergence_dx && std::fabs(deltaJ) > o->convergence_dj) || linFail)) {
+  for (kb::pol_pre<true>(&c); !c.done;) {
     const auto t_pass = std::chrono::steady_clock::now();
-    if (prevFailed) {
-      pol_J = J;
-    } else {
-      pol_pJ = last_succ;
-      last_succ = J;
-      pol_J = J;
-    }
-    if (!first) {  // the radius update (:33-59)
-      const double rho = (pol_pJ - pol_J) / s.L0;
-      if (rho > 0.75) {
-        const double n3 = 3 * s.dx_norm;
-        if (!(s.delta > n3)) s.delta = n3;
-      } else if (rho > 0 && rho < 0.25) {
-        s.delta /= 2.0;
-      } else if (rho <= 0) {
-        s.delta = s.step_type == 1 ? s.dx_gn_norm / 2.0 : s.delta / 2.0;
-      }
-    }
-    first = false;
-    if (!prevFailed) {  // rebuild + steepest descent only after an accepted step (:63-79)
+    if (c.do_build) {  // rebuild + steepest descent only after an accepted step (:63-79)
       if (launch_build(h)) return -1;
       sp_dl_launch_sd(h);
       KSP_HIP(hipGetLastError());
       if (read_scalars(h)) return -1;
-      sp_dl_set_sd(s, h->host_sc[SC_GG], h->host_sc[SC_GHG]);
+      kb::dl_set_sd(&s, h->host_sc[SC_GG], h->host_sc[SC_GHG]);
     }
     bool ok = true;
-    if (!sp_dl_sd_branch(s) && !s.gn_held) {
+    if (!kb::dl_sd_branch(&s) && !s.gn_held) {
       if (sp_dl_launch_gn(h)) return -1;
       KSP_HIP(hipGetLastError());
       if (read_scalars(h)) return -1;
       ok = h->host_sc[SC_OK] != 0.0;
-      if (ok) {
-        s.gn2 = h->host_sc[SC_GN2];
-        s.ggn = h->host_sc[SC_GGN];
-        s.dx_gn_norm = std::sqrt(s.gn2);
-        s.gn_held = true;
-      }
+      if (ok) kb::dl_hold_gn(&s, h->host_sc[SC_GN2], h->host_sc[SC_GGN]);
     }
-    int accepted = 0;
-    if (!ok) {  // deviation 2: a failed iteration without a step, retried on the next pass
-      prevFailed = true;
-      linFail = true;
-      out->failed_iterations++;
-    } else {
-      sp_dl_select(s, J);
+    double red[4] = {0.0, 0.0, 0.0, 0.0};  // cost and max |dx| of the candidate
+    if (ok) {  // (not ok: deviation 2, a failed iteration without a step, retried on the next pass)
+      kb::dl_select(&s, c.J);
       hipLaunchKernelGGL(k_sp_dl_step, dim3(d.n), dim3(64), 0, h->stream, d, h->dl, d.dx, s.a, s.b, s.step_type, 1);
       if (launch_cost(h, 1)) return -1;
       KSP_HIP(hipGetLastError());
       if (read_scalars(h)) return -1;
-      J = h->host_sc[SC_COST];
-      deltaX = h->host_sc[SC_DX];
-      deltaJ = p_J - J;
-      if (deltaJ < 0.0) {  // revertLastStateUpdate; the next pass keeps the system and the GN step
-        hipLaunchKernelGGL(k_sp_revert, dim3((h->S + 255) / 256), dim3(256), 0, h->stream, d);
-        out->failed_iterations++;
-        prevFailed = true;
-      } else {
-        p_J = J;
-        prevFailed = false;
-        accepted = 1;
-      }
-      out->iterations++;
+      red[0] = h->host_sc[SC_COST];
+      red[3] = h->host_sc[SC_DX];
     }
-    h->trace.push_back(ok ? J : NAN);
+    const kb::KbPassEnd e = kb::pol_accept<true>(&c, ok, red);
+    if (ok && !e.accepted)  // revertLastStateUpdate; the next pass keeps the system and the GN step
+      hipLaunchKernelGGL(k_sp_revert, dim3((h->S + 255) / 256), dim3(256), 0, h->stream, d);
+    h->trace.push_back(e.J);
     h->trace.push_back(s.delta);  // the lambda column carries delta
-    h->trace.push_back(deltaX);
-    h->trace.push_back(accepted);
-    const double t[kSpDlTrace] = {s.delta, ok ? (double)s.step_type : -1.0, s.beta, s.L0, s.dx_sd_norm, s.dx_gn_norm};
-    h->dl_trace.insert(h->dl_trace.end(), t, t + kSpDlTrace);
+    h->trace.push_back(e.dX);
+    h->trace.push_back(e.accepted);
+    const double t[kb::kDlTrace] = {s.delta, ok ? (double)s.step_type : -1.0, s.beta, s.L0, s.dx_sd_norm, s.dx_gn_norm};
+    h->dl_trace.insert(h->dl_trace.end(), t, t + kb::kDlTrace);
+    c.passes++;
+    kb::pol_pre<true>(&c);
+    if (!c.done) {
+      kb::dl_radius(&s, (c.pol_pJ - c.pol_J) / s.L0);  // get_dJ() / _L0
+      c.do_build = !c.prev_failed;
+    }
     h->dl_pass_ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_pass).count());
-    out->passes++;
   }
   KSP_HIP(hipStreamSynchronize(h->stream));
   h->built = h->solved = false;
-  out->J_final = p_J;
-  out->dx_final = deltaX;
-  out->dj_final = deltaJ;
-  out->linear_solver_failure = linFail;
+  sp_fill_solution(c, out);
   return 0;
 }
 }  // namespace
@@ -447,7 +341,7 @@ int kb_sp_set_dogleg_options(kb_sp_handle* h, const kb_dogleg_options* opts) {
   if (!h) return fail("kb_sp_set_dogleg_options: null");
   const kb_dogleg_options def{0.0};
   const kb_dogleg_options o = opts ? *opts : def;
-  if (!(o.delta_init >= 0.0) || !std::isfinite(o.delta_init))
+  if (!kb::dl_delta_valid(o.delta_init))
     return fail("kb_sp_set_dogleg_options: delta_init must be finite and >= 0");
   h->dl_opts = o;
   return 0;
@@ -456,15 +350,15 @@ int kb_sp_set_dogleg_options(kb_sp_handle* h, const kb_dogleg_options* opts) {
 int kb_sp_dogleg_step(kb_sp_handle* h, double delta, double* dx_out, kb_dogleg_info* info, int* ok) {
   if (!h || !ok) return fail("kb_sp_dogleg_step: null");
   if (!h->built) return fail("kb_sp_dogleg_step: build first");
-  if (!(delta >= 0.0) || !std::isfinite(delta)) return fail("kb_sp_dogleg_step: delta must be finite and >= 0");
+  if (!kb::dl_delta_valid(delta)) return fail("kb_sp_dogleg_step: delta must be finite and >= 0");
   KSP_HIP(hipSetDevice(h->device));
   if (sp_dl_ensure(h)) return -1;
-  SpDlState s;
-  s.delta = delta;
+  kb::KbDl s;
+  kb::dl_start(&s, delta);
   sp_dl_launch_sd(h);
   KSP_HIP(hipGetLastError());
   if (read_scalars(h)) return -1;
-  sp_dl_set_sd(s, h->host_sc[SC_GG], h->host_sc[SC_GHG]);
+  kb::dl_set_sd(&s, h->host_sc[SC_GG], h->host_sc[SC_GHG]);
   const double J = h->host_sc[SC_COST_BUILD];
   auto fill = [&](bool stepped) {
     if (!info) return;
@@ -476,7 +370,7 @@ int kb_sp_dogleg_step(kb_sp_handle* h, double delta, double* dx_out, kb_dogleg_i
     info->dx_gn_norm = s.dx_gn_norm;
     info->L0_over_J = stepped ? s.L0 / J : 0.0;
   };
-  if (!sp_dl_sd_branch(s)) {  // the GN step: dx, the solved flag and the scalars as a kb_sp_solve at lambda = 0 leaves them
+  if (!kb::dl_sd_branch(&s)) {  // the GN step: dx, the solved flag and the scalars as a kb_sp_solve at lambda = 0 leaves them
     if (sp_dl_launch_gn(h)) return -1;
     KSP_HIP(hipGetLastError());
     if (read_scalars(h)) return -1;
@@ -486,12 +380,9 @@ int kb_sp_dogleg_step(kb_sp_handle* h, double delta, double* dx_out, kb_dogleg_i
       fill(false);
       return 0;
     }
-    s.gn2 = h->host_sc[SC_GN2];
-    s.ggn = h->host_sc[SC_GGN];
-    s.dx_gn_norm = std::sqrt(s.gn2);
-    s.gn_held = true;
+    kb::dl_hold_gn(&s, h->host_sc[SC_GN2], h->host_sc[SC_GGN]);
   }
-  sp_dl_select(s, J);
+  kb::dl_select(&s, J);
   // the step into the query's own buffer; dmax is the one thing of a solve it rewrites (the next solve writes it again)
   hipLaunchKernelGGL(k_sp_dl_step, dim3(h->d.n), dim3(64), 0, h->stream, h->d, h->dl, h->dl.qdx, s.a, s.b, s.step_type, 0);
   KSP_HIP(hipGetLastError());
@@ -505,8 +396,8 @@ int kb_sp_dogleg_step(kb_sp_handle* h, double delta, double* dx_out, kb_dogleg_i
 
 int kb_sp_get_dogleg_trace(kb_sp_handle* h, double* out, int32_t cap) {
   if (!h || !out) return fail("kb_sp_get_dogleg_trace: null");
-  const int n = std::min<int>(cap, (int)(h->dl_trace.size() / kSpDlTrace));
-  if (n > 0) std::memcpy(out, h->dl_trace.data(), sizeof(double) * kSpDlTrace * n);
+  const int n = std::min<int>(cap, (int)(h->dl_trace.size() / kb::kDlTrace));
+  if (n > 0) std::memcpy(out, h->dl_trace.data(), sizeof(double) * kb::kDlTrace * n);
   return n;
 }
 
