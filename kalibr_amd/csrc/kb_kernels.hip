@@ -1204,6 +1204,19 @@ template <unsigned MM, int MW, bool WT>
 constexpr bool buildp_view_once() {
   return !WT && (MW == 8 ? __builtin_popcount(MM) <= 2 : mm_nintr<MM>() != 0);
 }
+// The block's frame-view entries in a per-lane vector loaded in the prologue (lane l: frame l of the block), the frame's
+// corner range taken by v_readlane: no global load in the view loop.  A family takes the form
+// only where it compiles without new scratch and at the parent's occupancy (profiles/r22/resource_usage.txt); every
+// other family keeps the load in the loop.  Those that take it: the all-VGPR families (buildp_vgpr_acc) except the
+// pinhole-equidistant and FOV view roles, which spill at the cap already, and except the table-less omni-radtan and
+// all-model ones, where the frame's transform is live in registers over the passes and the vector's two go to scratch.
+template <unsigned MM, int MW, bool WT, bool VT>
+constexpr bool buildp_fview_lanes() {
+  if (!buildp_vgpr_acc<MM, MW, WT>()) return false;
+  if (MM == (1u << KB_PINHOLE_EQUI) || MM == (1u << KB_PINHOLE_FOV)) return false;
+  if (!VT && (MM == (1u << KB_OMNI_RADTAN) || __builtin_popcount(MM) > 2)) return false;
+  return true;
+}
 
 // MW: the most waves a block may have.  12 (8 cameras + 4 frame waves) caps the kernel at 168 VGPRs, so that two
 // 6-wave blocks share a CU; rigs with N + frame waves <= 8 whose view role compiles two projection models
@@ -1265,7 +1278,11 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
   double tv[kTgU];
 #pragma unroll
   for (int u = 0; u < kTgU; ++u) tv[u] = d.target[min(tid + u * nth, nt3 - 1)];
-  const int2 fvl = d.fview[(size_t)f0 * N + cam + zl];
+  // the corner ranges of the wave's camera over the block's frames, one frame per lane (lane l: frame f0 + l of the
+  // first 64): the view loop takes each frame's range with v_readlane and holds no global load of its own
+  // (buildp_fview_lanes; the other families load frame f0's entry alone, and the next frame's in the loop)
+  constexpr bool fvlanes = buildp_fview_lanes<MM, MW, WT, VT>();
+  int2 fvl = d.fview[(size_t)(f0 + (fvlanes ? min(lane, G - 1) : 0)) * N + cam + zl];
   // this thread's column-table entry (a run-time-indexed kernel argument: the compiler reads it with a vector load)
   const int ctv = (tid < N) ? cam_arg(d.col_intr, tid) : cam_arg(d.col_base, tid - N);
   // GN fused: the previous solve's frame steps are applied here, and H_ff / H_fc are not stored (only the per-call
@@ -1421,6 +1438,9 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
       if (tid + u * nth < nt3) tg[tid + u * nth] = tv[u];
     for (int q = tid + kTgU * nth; q < nt3; q += nth) tg[q] = d.target[q];
   }
+  // (a flat pointer: its loads count on both wait counters, so the wait for a target corner also drains the next pass's
+  // cid / y prefetch.  Plain LDS reads as a compile-time fact of the table instantiations, which leave the prefetch in
+  // flight, measured inside the run-to-run bar: DESIGN.md 3c, round 22)
   const double* tgt = tg_lds ? tg : d.target;
   (void)tgt;
   const double lam2 = lam * lam;
@@ -1482,7 +1502,8 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
         const int mrow = lane >> 4, mcol = lane & 15;
         if (wave == 0 && it < 8) KB_TSB(d, 2 + 2 * it);
         double* vb = (it & 1) ? VB1 : VB;
-        const int2 fvn = d.fview[(size_t)min(f + 1, f1 - 1) * N + cam];  // the next frame's view (first loads below)
+        int2 fvn = {0, 0};  // the next frame's view (first loads below)
+        if constexpr (!fvlanes) fvn = d.fview[(size_t)min(f + 1, f1 - 1) * N + cam];
         // T_cam_w = (R | t) and the chain G of the view: from the block's table (a wave-uniform record: all reads
         // issued, then used), or computed here by every lane where the block has no table
         double R[9], t[3], tm[3] = {0.0, 0.0, 0.0};
@@ -1521,6 +1542,11 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
         const bool stv = (wave == 0 || wave == N - 1) && it == 2;  // diagnostic stamps: one steady-state frame
         const int sto = wave == 0 ? 130 : 160;
 #ifdef KB_STAMPS
+        if (stv) {  // the frame's corner range in hand (scalar registers)
+          KB_KEEPS(o0);
+          KB_KEEPS(o1);
+          KB_TSB(d, wave == 0 ? 80 : 84);
+        }
         if (stv) {  // the transform in hand, not only its reads issued
 #pragma unroll
           for (int q = 0; q < 9; ++q) KB_KEEP(R[q]);
@@ -1552,7 +1578,8 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
           // flips of J_delta = -Jp [I | [p]x] and of the intrinsic rows -Jp, -Jd (CameraDesignVariable.hpp(impl):38-54)
           // are not spent.  Lanes past the view's last corner keep zero rows (projecting a clamped corner on them
           // instead, without the exec-mask branch and the zero initialisation, spilled more VGPRs to AGPRs: k_buildp
-          // 93.1 -> 96.9 us).
+          // 93.1 -> 96.9 us; no initialisation and zeros stored by the lanes past the last corner under a branch of
+          // their own: 25 moves less per pass and 1.4 % slower at configs[3]).
           const bool valid = k < o1;
           double xu[16], xv[16];
 #pragma unroll
@@ -1717,6 +1744,14 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
         }
         if (o1 <= o0) make_g();  // a view without corners (no pass ran)
         {  // the next frame's first corner ids and keypoints, in flight during the expansion and the barrier
+          // the next frame's view from the block's vector (lane l: frame 64 c + l of the block); only blocks of more
+          // than 64 frames reload it, where the next frame starts a group of 64
+          if constexpr (fvlanes) {
+            const int nx = min(it + 1, G - 1);
+            if (nx > it && (nx & 63) == 0) fvl = d.fview[(size_t)(f0 + min(nx + lane, G - 1)) * N + cam];
+            fvn.x = __builtin_amdgcn_readlane(fvl.x, nx & 63);
+            fvn.y = __builtin_amdgcn_readlane(fvl.y, nx & 63);
+          }
           fv = fvn;
           const int k = min(fvn.x + lane, max(fvn.y - 1, 0));
           cidn = d.cid[k];

@@ -34,6 +34,8 @@ for w, o in (("wave 0", 130), ("last view wave", 160)):
         names[o + 4 * ps + 3] = f"  [{w}] f2 pass {ps} v MFMAs done"
     names[o + 8] = f"  [{w}] f2 expansion done"
     names[o + 9] = f"  [{w}] f2 transform ready"
+for w, o in (("wave 0", 80), ("last view wave", 84)):  # the head of a steady frame (with "transform ready" above)
+    names[o] = f"  [{w}] f2 corner range in hand"
 names[18] = "prologue: round-1 values in hand"
 names[19] = "prologue: frame steps done, poses staged"
 for w in range(4):
