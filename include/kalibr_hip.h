@@ -389,6 +389,12 @@ int kb_build_kernel_name(kb_handle* h, char* buf, int32_t cap);
  * k_build, the table does not fit the block's LDS at the current frame count, or KB_BUILDP_VIEWTAB=0 was set at
  * kb_create.  Read-only; the value can change with kb_append_frames / kb_drop_last_frames and the robust setters. */
 int kb_build_viewtab(kb_handle* h);
+/* 1 when this handle runs its fused Gauss-Newton passes in two launches per pass, the camera solve of pass i at the
+ * head of pass i + 1's k_buildp (expanded partials, C > 64, one unweighted rank, a kernel family that has the
+ * instantiation, a rig whose solve window fits the block's LDS); 0 when it keeps three launches per pass (sharded and
+ * weighted handles, C <= 64, the other policies, or KB_GN_SOLVE_IN_BUILD=0 at kb_create).  Read-only; the value can
+ * change with kb_append_frames / kb_drop_last_frames, the robust setters and kb_comm_init*. */
+int kb_gn_solve_in_build(kb_handle* h);
 
 /* Multi-GPU (frame sharding): each rank's handle holds its own frames;
  * the camera-block [S | b] and the cost/step statistics are all-reduced over RCCL once

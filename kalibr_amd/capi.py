@@ -26,7 +26,7 @@ EXPORTS = [
     "kb_get_state_flat", "kb_debug_chains", "kb_state_size", "kb_num_cols", "kb_camera_cols", "kb_eval_cost", "kb_build",
     "kb_set_constant_conditioner", "kb_set_conditioner", "kb_solve", "kb_get_rhs", "kb_rhs_jtj_rhs", "kb_covariance", "kb_reprojection_error_stats", "kb_apply_update", "kb_revert", "kb_get_normal_blocks",
     "kb_optimize", "kb_get_trace", "kb_set_dogleg_options", "kb_dogleg_step", "kb_get_dogleg_trace", "kb_run_gn_iterations", "kb_gn_prepare", "kb_gn_launch", "kb_build_kernel_stats",
-    "kb_build_kernel_name", "kb_build_viewtab", "kb_comm_get_unique_id", "kb_gn_pass_times", "kb_append_frames", "kb_drop_last_frames", "kb_optimize_marginal", "kb_optimize_marginal_analyze",
+    "kb_build_kernel_name", "kb_build_viewtab", "kb_gn_solve_in_build", "kb_comm_get_unique_id", "kb_gn_pass_times", "kb_append_frames", "kb_drop_last_frames", "kb_optimize_marginal", "kb_optimize_marginal_analyze",
     "kb_comm_init", "kb_comm_init_local", "kb_comm_direct", "kb_xar_export", "kb_xar_test", "kb_selftest_mfma", "kb_solve_marginal", "kb_analyze_marginal",
     # robust terms (kb_set_corner_invR is in EXPORTS_MIXED_CASE below)
     "kb_set_mestimator", "kb_get_mestimator_weights", "kb_set_robust_build",
@@ -141,7 +141,12 @@ def lib():
         L.kb_create.argtypes = [C.POINTER(Layout)]
         L.kb_destroy.argtypes = [C.c_void_p]
         L.kb_last_error.restype = C.c_char_p
+        # a measurement variant may be built from an older tree (the parent commit's library of an A/B run): a query
+        # it does not have yet is skipped there; the product library must export every name
+        older = bool(os.environ.get("KB_VARIANT_LIB"))
         for name in EXPORTS + EXPORTS_MIXED_CASE:
+            if older and name == "kb_gn_solve_in_build" and not hasattr(L, name):
+                continue
             fn = getattr(L, name)
             if name not in ("kb_create", "kb_destroy", "kb_last_error", "kb_sp_create", "kb_sp_destroy"):
                 fn.restype = C.c_int
@@ -178,6 +183,8 @@ def lib():
         L.kb_gn_launch.argtypes = [C.c_void_p, C.c_int32, dp]
         L.kb_build_kernel_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
         L.kb_build_viewtab.argtypes = [C.c_void_p]
+        if hasattr(L, "kb_gn_solve_in_build"):
+            L.kb_gn_solve_in_build.argtypes = [C.c_void_p]
         L.kb_build_kernel_stats.argtypes = [C.c_void_p, dp, dp, dp]
         L.kb_gn_pass_times.argtypes = [C.c_void_p, C.c_int32, dp, dp]
         L.kb_append_frames.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, dp, C.c_void_p, C.c_void_p,
@@ -530,6 +537,16 @@ class Solver:
     def build_viewtab(self):
         """True when the handle's k_buildp launches carry the per-view LDS table (kb_build_viewtab)"""
         r = lib().kb_build_viewtab(self.h)
+        if r < 0:
+            _check(r)
+        return bool(r)
+
+    def gn_solve_in_build(self):
+        """True when the handle's fused GN passes run the camera solve at the head of the next build kernel: two
+        launches per pass instead of three (kb_gn_solve_in_build)"""
+        if not hasattr(lib(), "kb_gn_solve_in_build"):  # an older measurement variant: three launches
+            return False
+        r = lib().kb_gn_solve_in_build(self.h)
         if r < 0:
             _check(r)
         return bool(r)

@@ -96,6 +96,47 @@ inline bool viewtab_fits(const Rig& r, bool pipe, int F) {
 constexpr int kViewtabMinFrames = 2;
 inline bool viewtab_pays(int gf) { return gf >= kViewtabMinFrames; }
 
+// The camera solve at the head of k_buildp (GN fused passes, expanded partials, C > 64: the SIB instantiations).  The
+// solve window overlays the start of the build's dynamic LDS: [0, kSolveCarveBytes) the solve's arrays (SolveCarve:
+// control block, dx_c, candidate intrinsics and chains; live until the build's prologue barrier), then
+// solve_body<0>'s dynamic map (image, factored tiles, inverses; dead once the solve returns).  Regions of the build:
+struct Region {
+  size_t lo, hi;  // bytes of the dynamic LDS
+};
+inline bool overlap(const Region& a, const Region& b) { return a.lo < b.hi && b.lo < a.hi; }
+// what is live ACROSS the solve (written before it, read after it): nothing -- the block issues its loads behind the solve
+// what is live from the solve to the prologue barrier: the carve
+inline Region solve_carve() { return {0, (size_t)kb_slay::kSolveCarveBytes}; }
+inline Region solve_window(int N, int C) {
+  return {0, (size_t)kb_slay::kSolveCarveBytes + kb_slay::lds_solve(N, C)};
+}
+// the view waves' tiles Xw, first written in the view loop, behind the prologue barrier
+inline Region tiles_region(int N) { return {0, sizeof(double) * (size_t)N * 64 * kXS}; }
+// what the prologue writes between the solve and its barrier while the carve is still read: the chain table K, the
+// staged target and frame poses, and the per-view table when the launch carries it (all behind the tiles; the image
+// part of the window below them is dead by then)
+inline Region prologue_region(const Rig& r, int gf, bool vt) {
+  const int CZ = 16 * kb_slay::nb(r.C);
+  const size_t vbs = 44 * r.N + 6 * CZ;
+  const size_t lo = sizeof(double) * ((size_t)r.N * 64 * kXS + r.N * 256 + r.N * 36 + vbs + 40 + 6 * CZ);
+  return {lo, vt ? viewtab_total(r, gf) : build_lds(r, true, gf, nullptr)};
+}
+// dynamic LDS (bytes) of a SIB launch: the build's, or the window where that is larger
+inline size_t sib_lds(const Rig& r, int gf, bool vt) {
+  const size_t b = vt ? viewtab_total(r, gf) : build_lds(r, true, gf, nullptr);
+  const size_t w = solve_window(r.N, r.C).hi;
+  return b > w ? b : w;
+}
+// a rig takes the SIB kernel at F frames: C beyond the one-wave solves, the carve inside the tiles (so nothing the
+// prologue writes touches it), and the whole within the block's share of the LDS (as viewtab_fits)
+inline bool sib_fits(const Rig& r, int F, bool vt) {
+  if (kb_slay::solve_cm(r.C) != 0 || !pipe_default(r.N)) return false;
+  const int bpc = r.bpc > 1 ? r.bpc : 1;
+  const int gf = gframes(true, bpc, F);
+  if (solve_carve().hi > tiles_region(r.N).hi || overlap(solve_carve(), prologue_region(r, gf, vt))) return false;
+  return sib_lds(r, gf, vt) + kBuildpStaticLds <= kLdsLimit / bpc;
+}
+
 // Robust terms (kb_set_mestimator / kb_set_corner_invR / kb_set_robust_build): the kernel a handle builds with.
 // `pipe0` is kb_create's choice for the unweighted handle; a weighted handle keeps it only in pipe mode
 // (KB_ROBUST_BUILD_PIPE: the weighted k_buildp), otherwise it builds with k_build.

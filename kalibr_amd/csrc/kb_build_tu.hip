@@ -39,6 +39,20 @@ const void* build_fn(int mb, bool pipe, bool wide, bool vt) {
                                                              : (const void*)k_build<7, GN, MM>;
 }
 
+// the GN fused k_buildp with the camera solve at its head (SIB), or null where the family has none: the pinhole-radtan
+// 12-wave family with four frame waves (the flagship's); a further family joins once tools/resource_usage.py shows it
+// without new scratch at the plain instantiation's occupancy
+const void* build_fn_sib(int mb, bool pipe, bool wide, bool vt) {
+  using namespace kb;
+  if constexpr (MM == (1u << KB_PINHOLE_RADTAN)) {
+    constexpr int MWN = kBuildpMaxCams + 4;
+    if (pipe && !wide && mb != 5)
+      return vt ? (const void*)k_buildp<7, true, MM, MWN, false, true, true>
+                : (const void*)k_buildp<7, true, MM, MWN, false, false, true>;
+  }
+  return nullptr;
+}
+
 // weighted handles (robust terms, kb_robust.hip) in KB_ROBUST_BUILD_GENERAL mode: k_build, the general (non-fused) pass only
 const void* build_fn_w(int mb) {
   using namespace kb;
@@ -75,6 +89,9 @@ const void* build_fn_pw(int mb, bool wide, bool vt) {
 #define KB_CAT(a, b) KB_CAT2(a, b)
 const void* KB_CAT(kb_build_fn_, KB_TU_ID)(bool gn, int mb, bool pipe, bool wide, bool vt) {
   return gn ? build_fn<true>(mb, pipe, wide, vt) : build_fn<false>(mb, pipe, wide, vt);
+}
+const void* KB_CAT(kb_build_fn_sib_, KB_TU_ID)(int mb, bool pipe, bool wide, bool vt) {
+  return build_fn_sib(mb, pipe, wide, vt);
 }
 const void* KB_CAT(kb_build_fn_w_, KB_TU_ID)(int mb) { return build_fn_w(mb); }
 const void* KB_CAT(kb_build_fn_pw_, KB_TU_ID)(bool gn, int mb, bool wide, bool vt) {

@@ -168,6 +168,11 @@ struct kb_handle {
   int mb = 7, ms = 7;  // Schur-sum tiles per wave of k_build / k_schur (template bucket)
   const void* fn_build = nullptr;
   const void* fn_build_gn = nullptr;  // GN fused passes
+  // GN fused passes with the previous pass's camera solve at the head of the build (k_buildp<.., SIB = true>): null
+  // where the handle keeps three launches per pass (set_build_kernels); KB_GN_SOLVE_IN_BUILD=0 (kb_create): never
+  const void* fn_build_sib = nullptr;
+  size_t lds_build_sib = 0;
+  bool sib_allowed = true;
   const void* fn_schur = nullptr;
   const void* fn_solve = nullptr;
   const void* fn_cov_cam = nullptr;  // k_cov_cam<CM> of fn_solve's CM
@@ -230,6 +235,7 @@ struct kb_handle {
 // k_build 1 | 4 | 7, or per frame wave of k_buildp 5 | 7).
 #define KB_BUILD_TU_DECL(id)                                            \
   const void* kb_build_fn_##id(bool gn, int mb, bool pipe, bool wide, bool vt); \
+  const void* kb_build_fn_sib_##id(int mb, bool pipe, bool wide, bool vt);      \
   const void* kb_build_fn_w_##id(int mb);                                       \
   const void* kb_build_fn_pw_##id(bool gn, int mb, bool wide, bool vt);
 KB_BUILD_TU_DECL(0)
@@ -255,6 +261,21 @@ static const void* pick_build(int mb, unsigned mm, bool pipe, bool wide, bool vt
     case 1u << KB_PINHOLE_FOV: return kb_build_fn_6(GN, mb, pipe, wide, vt);
     case (1u << KB_OMNI_RADTAN) | (1u << KB_EUCM): return kb_build_fn_7(GN, mb, pipe, wide, vt);
     default: return kb_build_fn_8(GN, mb, pipe, wide, vt);
+  }
+}
+
+// The GN fused k_buildp with the camera solve at its head, or null where the rig's family has none (kb_build_tu.hip).
+static const void* pick_build_sib(int mb, unsigned mm, bool pipe, bool wide, bool vt) {
+  switch (mm) {
+    case 1u << KB_PINHOLE_RADTAN: return kb_build_fn_sib_0(mb, pipe, wide, vt);
+    case 1u << KB_OMNI_RADTAN: return kb_build_fn_sib_1(mb, pipe, wide, vt);
+    case 1u << KB_EUCM: return kb_build_fn_sib_2(mb, pipe, wide, vt);
+    case 1u << KB_OMNI: return kb_build_fn_sib_3(mb, pipe, wide, vt);
+    case 1u << KB_DS: return kb_build_fn_sib_4(mb, pipe, wide, vt);
+    case 1u << KB_PINHOLE_EQUI: return kb_build_fn_sib_5(mb, pipe, wide, vt);
+    case 1u << KB_PINHOLE_FOV: return kb_build_fn_sib_6(mb, pipe, wide, vt);
+    case (1u << KB_OMNI_RADTAN) | (1u << KB_EUCM): return kb_build_fn_sib_7(mb, pipe, wide, vt);
+    default: return kb_build_fn_sib_8(mb, pipe, wide, vt);
   }
 }
 
@@ -498,6 +519,7 @@ static void set_build_kernels(kb_handle* h) {
   unsigned mm = 0;
   for (int i = 0; i < h->N; ++i) mm |= 1u << d.model[i];
   const bool vt = h->build_pipe && h->viewtab;  // the instantiations that carry the per-view table (build_lds decides)
+  h->fn_build_sib = nullptr;
   if (weighted(h) && h->build_pipe) {
     h->fn_build = pick_build_pw<false>(h->mb, mm, h->buildp_wide, vt);
     h->fn_build_gn = pick_build_pw<true>(h->mb, mm, h->buildp_wide, vt);
@@ -509,6 +531,18 @@ static void set_build_kernels(kb_handle* h) {
   }
   h->fn_build = pick_build<false>(h->mb, mm, h->build_pipe, h->buildp_wide, vt);
   h->fn_build_gn = pick_build<true>(h->mb, mm, h->build_pipe, h->buildp_wide, vt);
+  // the solve at the head of the build: expanded partials on one unweighted rank, a family that has the instantiation,
+  // and a rig whose solve window fits (kb_build_layout.h sib_fits); everything else keeps three launches per pass
+  if (h->sib_allowed && h->gn_fuse && h->xexp && h->build_pipe && h->nranks <= 1 && !h->comm && !h->lg &&
+      kb_blay::sib_fits(layout_rig(h), h->F, vt)) {
+    h->fn_build_sib = pick_build_sib(h->mb, mm, h->build_pipe, h->buildp_wide, vt);
+    h->lds_build_sib = kb_blay::sib_lds(layout_rig(h), h->d.gframes, vt);
+    if (h->fn_build_sib &&
+        hipFuncSetAttribute(h->fn_build_sib, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_build_sib) != hipSuccess) {
+      hipGetLastError();
+      h->fn_build_sib = nullptr;
+    }
+  }
 }
 
 // A change of the robust settings: a weighted handle builds with k_build (the layout KB_BUILD_PIPE=0 gives: frames
@@ -671,6 +705,7 @@ kb_handle* kb_create(const kb_layout* L) {
   // XCD can read it torn across cache lines (seen once as a diverged LM run on configs[3])
   d.fold = 0;
   if (const char* e = std::getenv("KB_GN_FUSED")) h->gn_fuse = std::atoi(e) != 0;
+  if (const char* e = std::getenv("KB_GN_SOLVE_IN_BUILD")) h->sib_allowed = std::atoi(e) != 0;
   d.dbg_stop = -1;
   d.dbg_flags = 0;
   rc |= h->alloc(&d.ticket, 16);
@@ -686,6 +721,7 @@ kb_handle* kb_create(const kb_layout* L) {
   rc |= h->alloc(&d.red_local, 8);
   d.red = d.red_local;
   rc |= h->alloc(&d.ctrl, 1);
+  rc |= h->alloc(&d.seam, 1);
   if (!solve_cm(h->C)) {  // k_solve<0>'s staged camera block (k_colimg / k_colsumx)
     d.img_n = img_n(h->C);
     rc |= h->alloc(&d.simg, (size_t)d.img_n);
@@ -1133,7 +1169,8 @@ static int launch_colsum(kb_handle* h, int gate, bool finish = true) {
 
 // use_mestimator false (kb_build(h, 0)): the kernel gets a copy of the parameters with the estimator off, so the
 // rows carry invR only (ErrorTerm.hpp(impl):178-180)
-static int launch_build(kb_handle* h, int gate, int fuse, bool use_mestimator = true) {
+// sib: the GN fused k_buildp that runs the previous pass's camera solve at its head (takes_sib)
+static int launch_build(kb_handle* h, int gate, int fuse, bool use_mestimator = true, bool sib = false) {
   KbDev& d = h->d;
   // per-call path: camera chains first; in the loop k_solve (or the loop start) computed them
   if (!gate) hipLaunchKernelGGL(k_pre, dim3(1), dim3(256), 0, h->stream, d, 0);
@@ -1145,6 +1182,10 @@ static int launch_build(kb_handle* h, int gate, int fuse, bool use_mestimator = 
     dp = &d_invr;
   }
   void* args[] = {dp, &gate, &fuse};
+  if (sib) {
+    KB_HIP(hipLaunchKernel(h->fn_build_sib, dim3(d.nblk), dim3(h->build_threads), args, h->lds_build_sib, h->stream));
+    return 0;
+  }
   KB_HIP(hipLaunchKernel(d.gn_fused ? h->fn_build_gn : h->fn_build, dim3(d.nblk), dim3(h->build_threads), args,
                          h->lds_build, h->stream));
   return 0;
@@ -1836,23 +1877,43 @@ static bool gn_fused(const kb_handle* h, int policy) {
   return policy == 1 && h->gn_fuse && (!weighted(h) || h->build_pipe);
 }
 
+// The handle runs its GN fused passes with the camera solve at the head of the next build (two launches per pass):
+// expanded partials on one unweighted rank, a kernel family and a rig that take it (set_build_kernels).  Sharded
+// handles (their all-reduce sits between the column sums and the solve), weighted handles, the other policies and
+// C <= 64 keep three launches.
+static bool takes_sib(const kb_handle* h, int policy) {
+  return gn_fused(h, policy) && h->fn_build_sib && h->xexp && !sharded(h) && !weighted(h);
+}
+
 // ev0 / ev1 (optional): HIP events recorded around the build kernel (kb_build_kernel_stats)
 static int enqueue_marg_pass(kb_handle* h);
 static int enqueue_dl_pass(kb_handle* h);
 
-static int enqueue_pass(kb_handle* h, int policy, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+// Pass i of a batch of n passes enqueued back to back (a captured graph, or an eager batch).  A handle that takes the
+// solve-in-build path (takes_sib) emits build | colsum for pass 0, (solve of pass i - 1 + build) | colsum for every
+// further pass and the plain k_solve behind the last one: the same kernels' work in the same order as n three-launch
+// passes, one linear chain.  The defaults (a batch of one) are the three-launch pass on every handle: the timing
+// queries that measure a build-only kernel enqueue their passes that way.
+static int enqueue_pass(kb_handle* h, int policy, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, int i = 0,
+                        int n = 1) {
   if (policy == kPolicyMarginal) return enqueue_marg_pass(h);
   if (policy == kPolicyDogleg) return enqueue_dl_pass(h);
   KbDev& d = h->d;
+  const bool sib = n > 1 && takes_sib(h, policy);
   auto build = [&]() -> int {
     if (ev0) KB_HIP(hipEventRecord(ev0, h->stream));
-    if (launch_build(h, 1, 1)) return -1;
+    if (launch_build(h, 1, 1, true, sib && i > 0)) return -1;
     if (ev1) KB_HIP(hipEventRecord(ev1, h->stream));
     return 0;
   };
   if (gn_fused(h, policy)) {
     GnFusedScope scope(h, true);
     const bool from_rows = h->d.Wp <= 2048;
+    if (sib) {  // (expanded partials: the column sums go straight to the image, from_rows does not apply)
+      // gate 2: the k_colsumx behind a solve-in-build kernel copies the control block it left in the seam
+      if (build() || launch_colsum(h, i > 0 ? 2 : 1, true)) return -1;
+      return i == n - 1 ? launch_solve(h, 1, 1, false) : 0;
+    }
     if (build() || launch_colsum(h, 1, !from_rows) || launch_solve(h, 1, 1, from_rows)) return -1;
     return 0;
   }
@@ -1938,7 +1999,7 @@ static int capture(kb_handle* h, int policy, int passes, hipGraphExec_t* out) {
   hipGraph_t g = nullptr;
   KB_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
   int rc = 0;
-  for (int i = 0; i < passes && !rc; ++i) rc = enqueue_pass(h, policy);
+  for (int i = 0; i < passes && !rc; ++i) rc = enqueue_pass(h, policy, nullptr, nullptr, i, passes);
   hipError_t e = hipStreamEndCapture(h->stream, &g);
   if (rc) return rc;
   if (e != hipSuccess) return fail(std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -1980,7 +2041,7 @@ static bool graph_ok(kb_handle* h, int policy) {
 static int launch_passes(kb_handle* h, int policy, int n, bool graph) {
   if (!graph) {
     for (int i = 0; i < n; ++i)
-      if (enqueue_pass(h, policy)) return -1;
+      if (enqueue_pass(h, policy, nullptr, nullptr, i, n)) return -1;
     return 0;
   }
   const int rem = n % kGraphPasses;
@@ -2401,7 +2462,7 @@ static int capture_gn(kb_handle* h, int passes, bool with_end, hipGraphExec_t* o
   hipGraph_t g = nullptr;
   KB_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
   int rc = 0;
-  for (int i = 0; i < passes && !rc; ++i) rc = enqueue_pass(h, 1);
+  for (int i = 0; i < passes && !rc; ++i) rc = enqueue_pass(h, 1, nullptr, nullptr, i, passes);
   if (!rc && with_end) rc = finish_pass(h, 1);
   const hipError_t e = hipStreamEndCapture(h->stream, &g);
   if (rc) {
@@ -2540,6 +2601,9 @@ static int timed_gn_passes(kb_handle* h, int n, std::vector<double>& pass_ms, st
     ~TsGuard() { hipFree(p); }
   } tsg{ts};
   // run = 0: build events, n passes; run = 1: pass stamps, n + 1 passes
+  // build_ms times a build-only kernel: run 0 enqueues three-launch passes on every handle (a handle that takes the
+  // solve-in-build path would otherwise time the camera solve with it); run 1 enqueues the passes as the loop runs
+  // them, so pass_ms is the pass the handle really takes
   auto enqueue_run = [&](int run) -> int {
     if (run == 0) {
       for (int r = 0; r < n; ++r)
@@ -2549,7 +2613,7 @@ static int timed_gn_passes(kb_handle* h, int n, std::vector<double>& pass_ms, st
     KbDev keep = h->d;
     h->d.pass_ts = ts;
     int rc = 0;
-    for (int r = 0; r <= n && !rc; ++r) rc = enqueue_pass(h, 1);
+    for (int r = 0; r <= n && !rc; ++r) rc = enqueue_pass(h, 1, nullptr, nullptr, r, n + 1);
     h->d = keep;
     return rc;
   };
@@ -2665,6 +2729,11 @@ int kb_build_kernel_name(kb_handle* h, char* buf, int32_t cap) {
   if (!h || !buf || cap < 1) return fail("kb_build_kernel_name: bad args");
   std::snprintf(buf, cap, "%s", h->build_pipe ? "k_buildp" : "k_build");
   return 0;
+}
+
+int kb_gn_solve_in_build(kb_handle* h) {
+  if (!h) return fail("kb_gn_solve_in_build: bad args");
+  return takes_sib(h, 1) ? 1 : 0;
 }
 
 int kb_build_viewtab(kb_handle* h) {

@@ -49,6 +49,11 @@ struct KbMarg {
   double* info;  // [8]: rank, sweeps, tolerance, sv gap, log2 sum of the first rank singular values, warm chain
 };
 
+struct KbSeam {
+  KbCtrl ctrl;
+  double camstat[4];
+};
+
 struct KbDev {
   int N, F, V, NC, C, ncols, S, K;  // K = target corners
   int off_base, off_frame;
@@ -133,6 +138,10 @@ struct KbDev {
   double rb_param;     // k | sigma^2 | sigma^2 | epsilon of the estimator
   int rb_kind;         // KB_MEST_*; 0: weight 1
   int rb_n;            // 0: no invR | 1: one matrix for every corner | NC: one per corner
+  // GN fused passes with the camera solve at the head of k_buildp: where block 0 leaves the control block and the
+  // camera step statistics of its solve.  No block writes ctrl or camstat in that launch (late blocks still read them
+  // at entry); the k_colsumx behind it takes its gate from here and copies both to their places (gate == 2)
+  KbSeam* seam;
 };
 
 #ifdef KB_STAMPS
@@ -143,10 +152,16 @@ struct KbDev {
   do {                          \
     if ((d).dbg_stop == (i)) return; \
   } while (0)
-// timeline stamp (100 MHz s_memrealtime) of thread 0 at point i of the last launch, without leaving the kernel
+// the same inside a function that returns a value
+#define KB_STAMPV(d, i, v)      \
+  do {                          \
+    if ((d).dbg_stop == (i)) return (v); \
+  } while (0)
+// timeline stamp (100 MHz s_memrealtime) of thread 0 at point i of the last launch, without leaving the kernel (block 0:
+// the solve at the head of k_buildp runs in every block of a grid)
 #define KB_TS(d, i)                                                                      \
   do {                                                                                   \
-    if (threadIdx.x == 0 && (d).dbg_ts) {                                                \
+    if (threadIdx.x == 0 && blockIdx.x == 0 && (d).dbg_ts) {                             \
       (d).dbg_ts[i] = __builtin_amdgcn_s_memrealtime();                                  \
       if ((i) == 0 || (i) == 7) (d).dbg_ts[60 + ((i) == 7)] = __builtin_amdgcn_s_memtime(); \
     }                                                                                    \
@@ -154,7 +169,7 @@ struct KbDev {
 // the same by lane 0 of whichever wave calls it (k_solve's update, pair-product and chain-writing waves: slots 128 ..)
 #define KB_TSW(d, i)                                                                           \
   do {                                                                                         \
-    if ((threadIdx.x & 63) == 0 && (d).dbg_ts) (d).dbg_ts[i] = __builtin_amdgcn_s_memrealtime(); \
+    if ((threadIdx.x & 63) == 0 && blockIdx.x == 0 && (d).dbg_ts) (d).dbg_ts[i] = __builtin_amdgcn_s_memrealtime(); \
   } while (0)
 // build-kernel timeline (k_buildp): lane 0 of the calling wave of block 0 stamps slot 64 + i
 #define KB_TSB(d, i)                                                                                       \
@@ -181,6 +196,9 @@ struct KbDev {
   } while (0)
 #define KB_STAMP(d, i) \
   do {                 \
+  } while (0)
+#define KB_STAMPV(d, i, v) \
+  do {                     \
   } while (0)
 #define KB_TS(d, i) \
   do {              \

@@ -340,6 +340,54 @@ struct ChainLds {
 // k_marg's tail keeps it at the start of its dynamic LDS (marg_lds_bytes, kb_solve_layout.h, which carries the size);
 // tests/marginal_cases.py restates it (CHAIN_LDS_BYTES) for the check that k_marg's LDS fits at every width
 static_assert(sizeof(ChainLds) == kChainLdsBytes, "ChainLds: update kChainLdsBytes and tests/marginal_cases.py");
+
+// The LDS of solve_body behind its dynamic image, as a struct of pointers: k_solve<CM> fills it from arrays of its own
+// (KB_SOLVE_LDS_OWN), k_buildp's solve-at-the-head instantiation from a SolveCarve at the start of its dynamic LDS
+constexpr int kCamstN = KB_MAX_CAMS * KB_MAX_INTR + 7 * (KB_MAX_CAMS - 1);
+struct SolveLds {
+  int* okl;
+  double* nbase;               // [KB_MAX_CAMS * 7] candidate baselines
+  int (*ctab)[KB_MAX_CAMS];    // [3] per camera: #intrinsics | first intrinsic column | baseline column
+  double* pubcol;              // [CM > 0 ? CM : 16] LDL^T column / solve broadcast (16-byte aligned)
+  int* fin;                    // [2] GN fused: done, cur after the previous pass's end
+  KbCtrl* cls;
+  double* cl_red;              // [4]
+  ChainLds* chl;               // CM == 0: the candidate chains' pair products (wave 1)
+  int* bflag;                  // CM == 0: baseline x published by the backsolve wave
+  double* xb;                  // CM == 0: [128] those x (rows >= 16 pub_tile)
+  double (*camst)[kCamstN];    // [2] the camera DVs of both state slots
+  // the solve at the head of k_buildp only (INB): what the block's build takes from LDS instead of HBM
+  double* dxl;                 // [128] dx_c
+  double* camn;                // [KB_MAX_CAMS * KB_MAX_INTR] the candidate intrinsics
+  double* cstat;               // [4] max|dx_c|, dx_c.dx_c, dx_c.g_c
+};
+// the same arrays as one record at the start of k_buildp's dynamic LDS (the solve window, kb_build_layout.h
+// solve_window: this record, then solve_body<0>'s image map); live until the build's prologue barrier
+struct alignas(16) SolveCarve {
+  double pubcol[16];
+  KbCtrl cls;
+  double cl_red[4], cstat[4];
+  double nbase[KB_MAX_CAMS * 7];
+  double xb[128], dxl[128];
+  double camn[KB_MAX_CAMS * KB_MAX_INTR];
+  double camst[2][kCamstN];
+  ChainLds chl;
+  int ctab[3][KB_MAX_CAMS];
+  int okl, fin[2], bflag;
+};
+static_assert(sizeof(SolveCarve) <= kSolveCarveBytes && kSolveCarveBytes % 16 == 0,
+              "SolveCarve: update kb_solve_layout.h kSolveCarveBytes");
+__device__ __forceinline__ SolveLds solve_lds_carve(SolveCarve* w) {
+  return {&w->okl, w->nbase, w->ctab, w->pubcol, w->fin, &w->cls, w->cl_red, &w->chl, &w->bflag, w->xb, w->camst,
+          w->dxl,  w->camn,  w->cstat};
+}
+// what solve_body tells its caller (the solve at the head of k_buildp acts on it; k_solve ends either way)
+constexpr int kSolveGo = 0;      // a step: dx_c, the candidate camera DVs and chains
+constexpr int kSolveDone = 1;    // the loop is over (at entry, or at the previous pass's end: this solve is discarded)
+constexpr int kSolveFailed = 2;  // non-positive pivot: the failed pass has ended (GN fused), nothing to apply
+template <int CM, bool INB = false>
+__device__ int solve_body(const KbDev& d, int gate, int do_update, int nth, const SolveLds& L, double* smw = nullptr);
+
 // part 1: the baselines and the pair products (threads tx < np; WAVE: one wave alone, wave-level LDS syncs)
 template <bool WAVE>
 __device__ __forceinline__ void chain_pairs(const KbDev& d, const double* base, ChainLds& L, int tx) {
@@ -1228,8 +1276,16 @@ constexpr bool buildp_fview_lanes() {
 //     the rest, kb_capi.hip build_lds): the view loop reads each view's transform and chain instead of computing them, and the
 //     per-frame computation is not compiled into it (as a run-time branch it kept its registers and cost the
 //     table-less path 1.6 % at configs[3], profiles/r16/).
-template <int TT, bool GNF, unsigned MM, int MW, bool WT = false, bool VT = false>
+// SIB: the camera solve of the previous pass at the head of the block (GN fused passes with expanded partials on one
+//     rank; the all-VGPR families only: with KB_MFMA_AGPR solve_body<0> spills under this kernel's register cap).
+//     Every block stages the k_solve image and runs solve_body<0, true> on waves 0..7 (the further waves take its
+//     barriers), in a window of the dynamic LDS that the build first writes after its prologue barrier
+//     (kb_build_layout.h solve_window); it then takes dx_c, the candidate intrinsics and chains and the control
+//     block from LDS.  Block 0 alone stores the solve's global results, and the control block into d.seam, not
+//     d.ctrl (what the fused kernel writes, and who reads it).
+template <int TT, bool GNF, unsigned MM, int MW, bool WT = false, bool VT = false, bool SIB = false>
 __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse) {
+  static_assert(!SIB || (GNF && buildp_vgpr_acc<MM, MW, WT>() && !WT), "SIB: unweighted all-VGPR GN instantiations");
   if constexpr (!buildp_vgpr_acc<MM, MW, WT>()) KB_MFMA_AGPR();
   pass_stamp(d);
   KbCtrl* c = d.ctrl;
@@ -1270,8 +1326,34 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
   int zl = 0;
   asm("" : "+v"(zl));
   const KbCtrl* cv = c + zl;
-  const int c_done = cv->done, c_dob = cv->do_build, c_cur = cv->cur, c_have = cv->have_dx;
-  const double c_lam = cv->lambda;
+  int c_done, c_dob, c_cur, c_have;
+  double c_lam;
+  SolveCarve* const sw = reinterpret_cast<SolveCarve*>(sm);  // SIB: the solve's arrays, live up to the prologue barrier
+  if constexpr (SIB) {
+    const SolveLds L = solve_lds_carve(sw);
+    const int st = solve_body<0, true>(d, gate, 1, nth, L, sm + kSolveCarveBytes / 8);
+    // block 0 hands the control block and the camera step statistics on (k_colsumx copies them to their places); a
+    // solve without a step leaves the statistics as they are
+    if (blockIdx.x == 0 && tid == 0) {
+      d.seam->ctrl = sw->cls;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) d.seam->camstat[q] = st == kSolveGo ? sw->cstat[q] : d.camstat[q];
+    }
+    if (st == kSolveDone) return;
+    __syncthreads();  // a failed solve: thread 0 ended the pass in cls behind solve_body's last barrier
+    if (wave == 0) KB_TSB(d, 17);  // solve done in block 0
+    c_done = sw->cls.done;
+    c_dob = sw->cls.do_build;
+    c_cur = sw->cls.cur;
+    c_have = sw->cls.have_dx;
+    c_lam = sw->cls.lambda;
+  } else {
+    c_done = cv->done;
+    c_dob = cv->do_build;
+    c_cur = cv->cur;
+    c_have = cv->have_dx;
+    c_lam = cv->lambda;
+  }
   const bool tg_lds = d.bp_tg;  // the host decides (its LDS budget holds a second view-output buffer)
   const int nt3 = 3 * d.K;
   constexpr int kTgU = 2;
@@ -1291,7 +1373,8 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
   double yr[6][2], dxv[2] = {0.0, 0.0}, bq = 0.0;
   if (gfu) {
 #pragma unroll
-    for (int sl = 0; sl < 2; ++sl) dxv[sl] = d.dx[min(lane + 64 * sl, C - 1)];  // masked after the pins (fdx_mask)
+    for (int sl = 0; sl < 2; ++sl)  // masked after the pins (fdx_mask)
+      dxv[sl] = SIB ? sw->dxl[min(lane + 64 * sl, C - 1)] : d.dx[min(lane + 64 * sl, C - 1)];
     fdx_load<false>(d, f0 + min(wave, G - 1), lane, yr, bq);  // wave j steps frame f0 + j (its rows in this round)
   }
   // the state-slot-indexed loads (camera chains and intrinsics of the build state, K_{i,j}, the block's first frame
@@ -1355,6 +1438,23 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
   // ---- round 2: loads indexed by round 1
   const double* sf = d.state + (size_t)cur * d.S;
   double* snew = d.state + (size_t)(1 - cur) * d.S;
+  // SIB: the candidate's chains and intrinsics come from this block's solve (block 0 stores them for later launches);
+  // with no step (a failed solve) the build state is slot cur, from HBM as ever
+  auto k_solved = [&](int q) {  // K_{i,j} entry q of the Kl order, as chain_write forms it
+    const int ee = q % 36, ij = q / 36, i = pair_row(ij), j = ij - i * (i - 1) / 2;
+    const double* P = sw->chl.PR[i * (i + 1) / 2 + j + 1];
+    return -chain_entry(P, P + 9, sw->chl.st[j], ee / 6, ee % 6);
+  };
+  if constexpr (SIB) {
+    if (upd) {
+      const int cm = min(tid / 22, N - 1), e = tid % 22;
+      const double v = e < 12 ? sw->chl.PR[cm * (cm + 1) / 2][e] : sw->camn[cm * KB_MAX_INTR + min(e - 12, KB_MAX_INTR - 1)];
+      csv[1] = csv[0] = v;
+#pragma unroll
+      for (int u = 0; u < 2; ++u) kv[1][u] = kv[0][u] = nK > 0 ? k_solved(min(tid + u * nth, nK - 1)) : 0.0;
+      if (blockIdx.x == 0) chain_write(d, sw->chl, 1 - cur, tid, nth);
+    }
+  }
   if (tid < N * 22) cst[tid / 22][tid % 22] = bs ? csv[1] : csv[0];
   if (tid < 2 * N) ctab[tid / N][tid % N] = ctv;
   // expanded partials (GN fused, C > 64, KbDev::xexp): the block expands its own per-camera sums in the epilogue
@@ -1392,6 +1492,12 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
     for (int q = tid + 2 * nth; q < nK; q += nth) {
       const int e = q % 36, ij = q / 36;
       const int i = pair_row(ij), j = ij - i * (i - 1) / 2;
+      if constexpr (SIB) {
+        if (upd) {
+          Kl[q] = k_solved(q);
+          continue;
+        }
+      }
       Kl[q] = Kc[(size_t)(i * N + j) * 36 + e];
     }
   }
@@ -1412,6 +1518,7 @@ __global__ void __launch_bounds__(64 * MW) k_buildp(KbDev d, int gate, int fuse)
   };
   // the wave's first frame, from the round-1 registers, outside the loop: a loop with loads in it waits for every
   // load in flight at its head, which would put the round-2 round trip in front of this step
+  if (wave == 0) KB_TSB(d, 61);  // frame steps start
   if (wave < G) {
     double fp[7];
 #pragma unroll
@@ -2302,12 +2409,21 @@ __global__ void __launch_bounds__(64 * kColsum1Waves) k_colsumx(KbDev d, int gat
   const bool mx = e >= d.Wp;
   const int ec = min(e, d.Wp);  // the block rows hold one max|dx_f| column (Wp); rank r's image slot takes it
   constexpr int U = 24;
-  const int done = c->done;
+  // gate == 2: behind a k_buildp that ran the camera solve at its head.  The control block and the camera step
+  // statistics of that solve are in d.seam (block 0 of that launch wrote them); the gate is taken from there, and one
+  // thread copies both to their places: only this thread of the launch touches ctrl and camstat
+  const bool seam = gate == 2;
+  const int done = seam ? d.seam->ctrl.done : c->done;
   double v[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) v[u] = d.part[(size_t)min(w + u * kColsum1Waves, d.nblk - 1) * d.Wr + ec];
 #pragma unroll
   for (int u = 0; u < U; ++u) KB_KEEP(v[u]);
+  if (seam && blockIdx.x == 0 && threadIdx.x == 0) {
+    *c = d.seam->ctrl;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) d.camstat[q] = d.seam->camstat[q];
+  }
   if (gate && done) return;
   double s = 0.0;
   for (int b0 = w; b0 < d.nblk; b0 += U * kColsum1Waves) {
@@ -4264,30 +4380,50 @@ __device__ bool schur_pcg(const KbDev& d, SGet sget, const double* b, int C, int
   return scal[0] != 0.0;
 }
 
+// solve_body's LDS arrays as a kernel's own (k_solve<CM>), named L for the call
+#define KB_SOLVE_LDS_OWN(L, CM)                                                       \
+  __shared__ int okl;                                                                 \
+  __shared__ double nbase[KB_MAX_CAMS * 7];                                           \
+  __shared__ int ctab[3][KB_MAX_CAMS];                                                \
+  __shared__ __attribute__((aligned(16))) double pubcol[(CM) > 0 ? (CM) : 16];        \
+  __shared__ int fin[2];                                                              \
+  __shared__ KbCtrl cls;                                                              \
+  __shared__ double cl_red[4];                                                        \
+  __shared__ ChainLds chl;                                                            \
+  __shared__ int bflag;                                                               \
+  __shared__ double xb[(CM) == 0 ? 128 : 1];                                          \
+  __shared__ double camst[2][kCamstN];                                                \
+  const SolveLds L = {&okl, nbase, ctab, pubcol, fin, &cls, cl_red, &chl, &bflag, xb, camst, nullptr, nullptr, nullptr};
+
 // Camera solve of one pass (one block): S = H_cc + lambda^2 I - sum Y^T Y, b = g_c - sum Y^T z staged in LDS,
 // LDL^T + solves (CM > 0: one-wave register LDL^T for C <= CM <= 64; CM == 0: block LDL^T in LDS), camera DV
 // update into state[1 - cur] and the camera chains of that candidate state into slot 1 - cur.
 // Every thread of the block must call it (barriers inside).
-template <int CM>
-__device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
+// INB: the solve at the head of a k_buildp block (every block of the grid runs it, bit for bit the same).  `sm` is then
+// the block's solve window, the global results are stored by block 0 alone, and the control block is left in L.cls: no
+// block writes d.ctrl, which late blocks of the grid still read at their entry.
+template <int CM, bool INB>
+__device__ int solve_body(const KbDev& d, int gate, int do_update, int nth, const SolveLds& L, double* smw) {
   KbCtrl* c = d.ctrl;
-  extern __shared__ __attribute__((aligned(16))) double sm[];
+  extern __shared__ __attribute__((aligned(16))) double sm_dyn[];
+  double* sm = INB ? smw : sm_dyn;
+  const bool blk0 = !INB || blockIdx.x == 0;  // stores the global results
   const int N = d.N, C = d.C, W = d.W, tid = threadIdx.x;
   const int Cp = C * (C + 1) / 2;
   const int nb = KB_SLAY_NB(C), n16 = 16 * nb;  // CM == 0: 16 x 16 tiles, rows 0 .. C (b appended as row C)
   // the packed layout (CM > 0) or the k_colimg image and the factored diagonal tiles behind it: kb_solve_layout.h
   KB_SLAY_SOLVE_MAP(double*, sm, CM > 0, N, C)  // S, bv, gl, Hs, T, K, Dfac, Xinv, rDv
   int* ci = (int*)cip;                           // [C]
-  __shared__ int okl;
-  __shared__ double nbase[KB_MAX_CAMS * 7];  // candidate baselines
-  __shared__ int ctab[3][KB_MAX_CAMS];       // per camera: #intrinsics | first intrinsic column | baseline column
-  __shared__ __attribute__((aligned(16))) double pubcol[CM > 0 ? CM : 16];  // LDL^T column / solve broadcast
-  __shared__ int fin[2];  // GN fused: done, cur after the previous pass's end
-  __shared__ KbCtrl cls;
-  __shared__ double cl_red[4];
-  __shared__ ChainLds chl;                     // CM == 0: the candidate chains' pair products (wave 1)
-  __shared__ int bflag;                        // CM == 0: baseline x published by the backsolve wave
-  __shared__ double xb[CM == 0 ? 128 : 1];     // CM == 0: those x (rows >= 16 pub_tile)
+  int& okl = *L.okl;
+  double* nbase = L.nbase;
+  int (*ctab)[KB_MAX_CAMS] = L.ctab;
+  double* pubcol = L.pubcol;
+  int* fin = L.fin;
+  KbCtrl& cls = *L.cls;
+  double* cl_red = L.cl_red;
+  ChainLds& chl = *L.chl;
+  int& bflag = *L.bflag;
+  double* xb = L.xb;
   if (CM == 0 && tid == 0) bflag = 0;
   // the control block is read once, here, so that its loads go out with the staging round: nothing in this kernel
   // writes ctrl before finish_prev (which reads and writes *c itself) and the previous kernel has completed, so this
@@ -4329,7 +4465,7 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
   }
   // the camera DVs of both state slots (the DV update reads slot cur, which the previous pass's end may still flip),
   // loaded with the staging round instead of one dependent round trip after the solves
-  __shared__ double camst[2][KB_MAX_CAMS * KB_MAX_INTR + 7 * (KB_MAX_CAMS - 1)];
+  double (*camst)[kCamstN] = L.camst;
   const int nst = N * KB_MAX_INTR + 7 * (N - 1);
   double cpv[2];
 #pragma unroll
@@ -4341,7 +4477,7 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
   // vector load, which belongs to the staging round too (unconditional; stored below by tid < 3 N)
   const int ctv = tid < N ? cam_arg(d.nintr, tid) : (tid < 2 * N ? cam_arg(d.col_intr, tid - N) : cam_arg(d.col_base, tid - 2 * N));
   KB_TS(d, 0);
-  KB_STAMP(d, 0);
+  KB_STAMPV(d, 0, kSolveDone);
   // phase A: stage K, column info, per-camera sums and the Schur sums in LDS (one row: psum)
   if constexpr (CM == 0) {
     // the k_colimg image (the complete system): one contiguous 16-byte copy, 12 loads in flight per thread (one round
@@ -4398,10 +4534,14 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
   if (tid == 0) okl = (csok != 0) && !(bv[C] > 0.0);
   // the loop's done flag (entry copy) is tested only here, behind the staging loads it was issued with; nothing
   // global has been written yet
-  if (gate && cdone) return;
+  if (gate && cdone) {
+    if constexpr (INB)
+      if (tid == 0) cls = *c;  // the caller's thread 0 reads it back (block 0 hands it on)
+    return kSolveDone;
+  }
   if (gate && !d.gn_fused && tid == 0) c->pending = 1;
   KB_TS(d, 1);
-  KB_STAMP(d, 1);
+  KB_STAMPV(d, 1, kSolveDone);
   // phase B: camera block expansion (CM == 0: done by k_colimg)
   if constexpr (CM > 0) {
     for (int q = tid; q < N * N * 36; q += nth) {
@@ -4431,11 +4571,11 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
       if (cl.have_dx) {
         cl_red[1] = cl_red[2] = 0.0;
         cl_red[3] = fmax(dxr, d.camstat[0]);
-        pol_post(&cl, d, cl_red);
+        pol_post(&cl, d, cl_red, blk0);
         if (!cl.done) pol_pre<true>(&cl);
         cl.have_dx = 0;
         cl.pending = 0;
-        *c = cl;
+        if constexpr (!INB) *c = cl;
       }
       fin[0] = cl.done;
       fin[1] = cl.cur;
@@ -4451,7 +4591,8 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
       const int i = lane + 64 * sl;
       if (i < C) {
         const double g = gl[i];
-        d.dx[i] = x[sl];
+        if (blk0) d.dx[i] = x[sl];
+        if constexpr (INB) L.dxl[i] = x[sl];
         mx = fmax(mx, fabs(x[sl]));
         dd += x[sl] * x[sl];
         dr += x[sl] * g;
@@ -4461,12 +4602,20 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
     dd = wave_sum_d(dd);
     dr = wave_sum_d(dr);
     if (lane == 0) {
+      if constexpr (INB) {  // handed on by block 0 (k_buildp), applied by this block's frame steps
+        L.cstat[0] = mx;
+        L.cstat[1] = dd;
+        L.cstat[2] = dr;
+        cls.have_dx = 1;
+        cls.pending = 1;
+      } else {
       d.camstat[0] = mx;
       d.camstat[1] = dd;
       d.camstat[2] = dr;
       if (gfu) {  // the step is applied by the next pass's build (or the finishing back-substitution)
         c->have_dx = 1;
         c->pending = 1;
+      }
       }
     }
     if (do_update) {
@@ -4493,7 +4642,15 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
         const int col = act ? ctab[1][cm] + xi : 0;
         const double v0 = __shfl(x[0], col & 63), v1 = __shfl(x[1], col & 63);
         const double dv = (col >> 6) ? v1 : v0;
+        if constexpr (INB) {
+          const double vn = vin[r] + (act ? dv : 0.0);
+          if (q < N * KB_MAX_INTR) {
+            L.camn[q] = vn;
+            if (blk0) out[q] = vn;
+          }
+        } else {
         if (q < N * KB_MAX_INTR) out[q] = vin[r] + (act ? dv : 0.0);
+        }
       }
       if (CM > 0 && N > 1) {  // CM == 0: wave 1 did the baselines (and the chains) beside the backsolve
         double d6[6], nb[7];
@@ -4528,7 +4685,7 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
   }
   __syncthreads();
   KB_TS(d, 3);
-  KB_STAMP(d, 2);
+  KB_STAMPV(d, 2, kSolveDone);
   if constexpr (CM > 0) {
 #ifdef KB_STAMPS
     const int reps = (d.dbg_flags & 1) ? 2 : 1;  // diagnostic: factor twice (rolled: same code, warm)
@@ -4545,8 +4702,8 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
     } else if (gfu && fwave) {
       finish_prev();
     }
-    KB_STAMP(d, 3);
-    KB_STAMP(d, 4);
+    KB_STAMPV(d, 3, kSolveDone);
+    KB_STAMPV(d, 4, kSolveDone);
   } else {
     // phase C: blocked LDL^T with the forward solve (row C); the previous pass's end beside the first panel
     KB_TS(d, 247);
@@ -4556,19 +4713,20 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
     // lies behind the factorisation's code: wave 0 then falls through towards panel 0 instead of branching over the
     // inlined schur_pcg (round 20: 0.44 us at that branch, 0.08 us without it; no instruction runs in between, so
     // presumably a fetch of instructions that are not cached at that point of a launch)
-    if (__builtin_expect(d.pcs_cb != nullptr, 0)) {
+    if (__builtin_expect(!INB && d.pcs_cb != nullptr, 0)) {  // (INB: the optimizer loop never takes this path)
       auto sget = [&](int i, int j) { return S[i >= j ? tidx(i, j) : tidx(j, i)]; };
       double* bcol = rDv;  // b (row C of the image) as a vector; rDv is unused without the LDL^T
       for (int j = tid; j < C; j += nth) bcol[j] = S[tidx(C, j)];
       __syncthreads();
-      if (!schur_pcg(d, sget, bcol, C, nth, x)) okl = 0;
+      if constexpr (!INB)
+        if (!schur_pcg(d, sget, bcol, C, nth, x)) okl = 0;
       __syncthreads();
       if (tid < 64 && okl && !(gfu && fin[0])) wave0_tail(gfu ? fin[1] : cur);
     } else {
     KB_TS(d, 249);
     ldl_panels(d, S, rDv, Dfac, Xinv, C, nb, &okl);  // ends with a block barrier: okl and fin are final
     KB_TS(d, 4);
-    KB_STAMP(d, 3);
+    KB_STAMPV(d, 3, kSolveDone);
     // phase D: Ltilde^T x = z on wave 0; wave 1 updates the baselines from the published baseline rows and builds the
     // candidate state's camera chains while wave 0 finishes the intrinsic rows (the baselines follow every intrinsic
     // column, so their rows are final first)
@@ -4595,7 +4753,7 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
           double* out = d.state + (size_t)(1 - cu) * d.S;
 #pragma unroll
           for (int q = 0; q < 7; ++q) {
-            out[d.off_base + 7 * lane + q] = nbv[q];
+            if (blk0) out[d.off_base + 7 * lane + q] = nbv[q];
             nbase[7 * lane + q] = nbv[q];
           }
         }
@@ -4607,16 +4765,25 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
       KB_TSW(d, 252);
     }
     }
-    KB_STAMP(d, 4);
+    KB_STAMPV(d, 4, kSolveDone);
   }
   __syncthreads();  // okl final
   KB_TS(d, 5);
   if (gfu) {
-    if (fin[0]) return;  // the loop ended at the previous pass: this solve is discarded
+    if (fin[0]) return kSolveDone;  // the loop ended at the previous pass: this solve is discarded
     cur = fin[1];
   }
   if (!okl) {
     if (tid == 0) {
+      if constexpr (INB) {  // cls is the control block after the previous pass's end (finish_prev)
+        KbCtrl& cl = cls;
+        cl.solve_ok = 0;
+        cl_red[0] = cl_red[1] = cl_red[2] = cl_red[3] = 0.0;
+        pol_post(&cl, d, cl_red, blk0);
+        if (!cl.done) pol_pre<true>(&cl);
+        cl.pending = 0;
+        cl.have_dx = 0;
+      } else {
       c->solve_ok = 0;
       if (gfu) {  // GN fused: the failed pass ends here (nothing to apply)
         KbCtrl& cl = cls;
@@ -4628,25 +4795,29 @@ __device__ void solve_body(const KbDev& d, int gate, int do_update, int nth) {
         cl.have_dx = 0;
         *c = cl;
       }
+      }
     }
-    return;
+    return kSolveFailed;
   }
   if (CM > 0 && tid < 64) wave0_tail(cur);  // CM == 0: ran right after the backsolve
   KB_TS(d, 6);
-  KB_STAMP(d, 5);
+  KB_STAMPV(d, 5, kSolveDone);
   if (CM > 0 && do_update) {
     __syncthreads();
     chain_block(d, nbase, 1 - cur, nth);  // chains of the candidate state (k_backsub's cost, next build if accepted)
   }
-  if (CM == 0 && do_update) chain_write(d, chl, 1 - cur, tid, nth);  // pair products by wave 1 before the barrier
+  // (INB: k_buildp stores them from block 0 once its own copies are taken)
+  if (CM == 0 && do_update && !INB) chain_write(d, chl, 1 - cur, tid, nth);  // pair products by wave 1 before the barrier
   KB_TS(d, 7);
+  return kSolveGo;
 }
 
 // CM > 0: 4 waves (one factors); CM == 0: 8 waves
 template <int CM>
 __global__ void __launch_bounds__(CM == 0 ? 512 : 256) k_solve(KbDev d, int gate, int do_update) {
   if constexpr (CM == 0) KB_MFMA_AGPR();
-  solve_body<CM>(d, gate, do_update, blockDim.x);  // returns early once ctrl->done (after its staging loads)
+  KB_SOLVE_LDS_OWN(L, CM)
+  solve_body<CM>(d, gate, do_update, blockDim.x, L);  // returns early once ctrl->done (after its staging loads)
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -26,6 +26,7 @@ constexpr int kMargMaxC = 112;            // capacity of k_marg's per-column arr
 constexpr int kMargThreads = 1024;
 constexpr int kMargLdsStage = 19000;  // dynamic LDS doubles up to which k_marg stages V0 in LDS too
 constexpr int kChainLdsBytes = 7680;  // sizeof(ChainLds) (kb_kernels.hip asserts it beside the struct)
+constexpr int kSolveCarveBytes = 16768;  // >= sizeof(SolveCarve), a multiple of 16 (kb_kernels.hip asserts both)
 static_assert(kMaxC <= kCovMaxC && kMaxC <= kMargMaxC, "the array capacities hold every admitted width");
 
 // ---- the selectors
