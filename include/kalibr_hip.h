@@ -506,9 +506,8 @@ int kb_sp_get_system(kb_sp_handle* h, double* Hcc, double* Hsc, double* Hband, d
  * first, so dx, the solved flag and the scalars are exactly as a kb_sp_solve under the same conditioner leaves them, and
  * the state is untouched.  It inverts the system kb_sp_build made: motion-error and prior terms are part of it, and so
  * are M-estimator weights and corner invR of a weighted handle (the reference's useMEstimator = false covariance is the
- * caller's to get, by clearing the estimators before the build).  Needs kb_sp_build.  Refused on a handle created under
- * KSP_PARTITION=1, KSP_ZS=0 or KSP_DEEP=1: only the default solve keeps every node's factor.  A KSP_ZSF=0 handle
- * returns the bits of a default one: the query sums the camera block's Schur complement in one fixed order itself.
+ * caller's to get, by clearing the estimators before the build).  Needs kb_sp_build.  A KSP_ZSF=0 handle returns the
+ * bits of a default one: the query sums the camera block's Schur complement in one fixed order itself.
  * kb_sp_curve_covariance: the same pipeline, then P [n][6][6], the covariance of the curve value [p | rotation vector]
  * at times[q] (linear in its four active coefficients, weights of derivative 0 as kb_sp_upload evaluates them); a time
  * outside the spline interval is refused before any launch. */

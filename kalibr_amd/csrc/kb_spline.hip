@@ -36,13 +36,8 @@
   do {                              \
     if (d.dbg_stop == (i)) return;  \
   } while (0)
-// timeline stamp (100 MHz s_memrealtime) of thread 0 of block 0 at slot i (tools/diag_sp_ts.py)
-#define KSP_TS(i)                                                                                          \
-  do {                                                                                                     \
-    if (blockIdx.x == 0 && threadIdx.x == 0 && d.dbg_ts && (i) < 320) d.dbg_ts[i] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-// the same for thread 0 of block b
-#define KSP_TSB(b, i)                                                                                      \
+// timeline stamp (100 MHz s_memrealtime) of thread 0 of block b at slot i (tools/diag_sp_levels.py)
+#define KSP_TSB(b, i)                                                                                     \
   do {                                                                                                     \
     if (blockIdx.x == (b) && threadIdx.x == 0 && d.dbg_ts && (i) < 320) d.dbg_ts[i] = __builtin_amdgcn_s_memrealtime(); \
   } while (0)
@@ -52,9 +47,6 @@
   } while (0)
 #define KSP_STOP(i) \
   do {              \
-  } while (0)
-#define KSP_TS(i) \
-  do {            \
   } while (0)
 #endif
 
@@ -73,7 +65,7 @@ constexpr int FPB = 2;      // frames per k_sp_frames block (600 blocks at confi
 constexpr int RW = 16;      // waves of the column-sum kernels (k_sp_reduce_cc, k_sp_schur_red)
 constexpr int XS = 17;      // LDS row stride of the 64 x 16 Jacobian-row tile
 constexpr int WI = 55;      // IMU theta partial row: 9x9 upper (45) | g (9) | cost
-constexpr int NPB = 4;      // nodes per k_sp_schur block
+constexpr int NPB = 4;      // nodes per block of the Schur sums (zschur_block)
 constexpr int TCH = 32;     // IMU samples staged per k_sp_assemble chunk
 constexpr int TCF = 8;      // frames staged per k_sp_assemble chunk
 constexpr int IRQ = 42;     // IMU record: T1 [9] | T2 [9] | T3 [9] | C^T [9] | e [6] (imu_sample)
@@ -87,7 +79,7 @@ enum { SC_COST_BUILD = 0, SC_OK = 1, SC_DX = 2, SC_COST = 3, SC_LAM2 = 4, SC_GHG
 
 struct SpDev {
   int N, C, K, F, M, n, m, n_target;
-  int nin[KB_MAX_CAMS], model[KB_MAX_CAMS], col_intr[KB_MAX_CAMS];
+  int nin[KB_MAX_CAMS], model[KB_MAX_CAMS];
   int col_pose[KB_MAX_CAMS];  // pose DV q: B_q (q < N-1), T_c0_b (q = N-1)
   int col_imu;
   int ckind[MAXC], cidx[MAXC], csub[MAXC];  // column -> (0 intr | 1 pose | 2 imu, cam / q, sub-index)
@@ -112,8 +104,8 @@ struct SpDev {
   double* ipart;          // [nblk_ic][WI]
   double* Hcc;            // [C][C] | gc [C] | cost
   double *D0, *U0, *R0;   // built node blocks [n][324], [n][324], [n][18 m]
-  double *D, *U, *R;      // working copies (cyclic reduction in place)
-  double *Lf, *Z, *X;     // [n][324], [n][18 (36 + m)], [n][18 m]
+  double *D, *R;          // working copies of D0, R0 (cyclic reduction in place, from the second level on)
+  double *Lf, *Z;         // every node's factor [n][324] and Z = L^-1 [U_l^T | U | R] [n][18 (36 + m)]
   double* Lid;            // [n][18] inverse diagonal of Lf
   double* spart;          // [nblk_s][Ws]
   double* dx;             // [C + 6K]
@@ -137,18 +129,17 @@ struct SpDev {
   const double* pp;       // [npos][3] prior
   const double* pW;       // [npos][9] invR
   const int* node_pp;     // [n][4] priors touching node i (b in [3i-3, 3i+2]) | owned by it (b in [3i, 3i+2])
-  long long* dbg_ts;      // diagnostics only: [320] KSP_TS stamps
+  long long* dbg_ts;      // diagnostics only: [320] KSP_TSB stamps
   int dbg_stop;           // diagnostics only (KSP_DBG_STOP): 0, or the phase after which the timed kernels return
   int zero_lam;           // GN pass: k_sp_imu_cc sets lambda^2 = 0 (no separate launch)
   int cc_fused;           // GN pass: k_sp_reduce_cc's column sums run as extra blocks of k_sp_elim1 (one launch less)
-  int zsf;                // zs: the Schur sums of nodes 1.. run as extra blocks of the top level's launch (beside its
-                          // one block), the top node's own term added by k_sp_schur_red
-  // round 6: the Schur complement from the forward reduction alone (S = H_tt - sum_i Z_R,i^T Z_R,i over every node's
-  // eliminated right-hand side, the top node's included) and the back substitution with ONE right-hand side
-  // v = [-dtheta | 1] after the camera solve (k_sp_bvec*), instead of X = D^-1 [H_st | g_s] for all C + 1 columns
-  int zs;
-  double* xs;             // [n][18] the nodes' spline steps x_j = X_j v (zs)
-  double* bm;             // [n][18][37] L_j^-T [Z_Uin,j | Z_U,j | Z_R,j v] (zs, k_sp_bprep)
+  int zsf;                // the Schur sums of nodes 1.. run as extra blocks of the top level's launch (beside its one
+                          // block), the top node's own term added by k_sp_schur_red
+  // the Schur complement comes from the forward reduction alone (S = H_tt - sum_i Z_R,i^T Z_R,i over every node's
+  // eliminated right-hand side, the top node's included) and the back substitution runs with ONE right-hand side
+  // v = [-dtheta | 1] after the camera solve (k_sp_bprep, k_sp_bvec*)
+  double* xs;             // [n][18] the nodes' spline steps x_j
+  double* bm;             // [n][18][37] L_j^-T [Z_Uin,j | Z_U,j | Z_R,j v] (k_sp_bprep)
   double* irec;           // [IRQ][M] per-sample IMU records (k_sp_imu_cc -> k_sp_assemble): T1 | T2 | T3 | C^T | e
   // robust terms (kb_sp_set_mestimator / kb_sp_set_corner_invR), read by the WT instantiations only
   int rw_kind[3];         // KB_MEST_* of the reprojection | gyro | accel terms (compile-time indices only: sp_cam_arg)
@@ -160,7 +151,7 @@ struct SpDev {
   int q_term;             // k_sp_weights only: the family (kb_sp_term) and its outputs
   double *q_w, *q_s;
   // covariance query (kb_sp_covariance): blocks of (H + lam2 I)^-1 by the selected inverse over the
-  // factors of a zs solve; allocated by the first query
+  // factors the solve leaves; allocated by the first query
   double* cvE;            // [n][18][54 + C] L_j^-T [Z_Uin | Z_U | Z_R[:, :C] | L_j^-1] = [M_l | M_r | M_theta | P_j]
   double* cvD;            // [n][324] Sigma_jj
   double *cvSl, *cvSr;    // [n][324] Sigma_j,j-s | Sigma_j,j+s, s the stride node j was eliminated at
@@ -1347,7 +1338,7 @@ __device__ __forceinline__ double ksp_recip1(double x) {
   return fma(r, fma(-x, r, 1.0), r);
 }
 
-// ---- the 18 x 18 Cholesky with the pivot-row broadcasts fused into the FMAs (chol18_dpp, the default)
+// ---- the 18 x 18 Cholesky with the pivot-row broadcasts fused into the FMAs (chol18_wave)
 // x += (lane L's y within the lane's 16-lane row) * f by one v_fmac_f64 with a DPP row_newbcast source (64-bit DPP,
 // gfx90a+); y may be x itself (operands are read before the write)
 template <int L>
@@ -1401,10 +1392,10 @@ __device__ __forceinline__ void chol18_steps(double (&dr)[NB], double (&br)[NB],
 // one-wave Cholesky of an 18 x 18 SPD matrix in LDS (row-major, both triangles), written back as the lower factor L
 // with id = 1 / diag(L).  Columns 0..15 as one panel: every 16-lane row of the wave holds rows 0..15 (lane r: row r)
 // and lanes 16, 17 also rows 16, 17 of the matrix; step K takes D_K and the pivot row from lane K of its own 16-lane row
-// by DPP (fused into the FMAs: no v_readlane / SGPR round trip, which the readlane version pays twice per broadcast
-// double).  Then the 2 x 2 trailing block (rows 16, 17) and the scaling W D^-1/2 -> L.  Returns false if not positive
+// by DPP (fused into the FMAs: no v_readlane / SGPR round trip, which a readlane broadcast pays twice per double).
+// Then the 2 x 2 trailing block (rows 16, 17) and the scaling W D^-1/2 -> L.  Returns false if not positive
 // definite.  Call from one whole wave.
-__device__ __forceinline__ bool chol18_dpp(double* A, double* id, int lane) {
+__device__ __forceinline__ bool chol18_wave(double* A, double* id, int lane) {
   const int r = lane & 15, g = lane >> 4;
   const int br_row = (g == 1 && r < 2) ? 16 + r : r;  // lanes 16, 17: rows 16, 17 (the others: a copy, unused)
   double dr[NB], br[NB], rs[16];
@@ -1465,50 +1456,6 @@ __device__ __forceinline__ bool chol18_dpp(double* A, double* id, int lane) {
   return ok;
 }
 
-// one-wave register Cholesky of an 18 x 18 SPD matrix held in LDS (lower, row-major): lane r keeps row r in
-// registers, column k broadcast by v_readlane; the factor is written back.  Returns false if not positive
-// definite.  Call from one whole wave.
-__device__ __forceinline__ bool chol18_wave(double* A, double* id, int lane) {
-#ifndef KSP_CHOL_READLANE
-  return chol18_dpp(A, id, lane);
-#endif
-  double a[NB];
-#pragma unroll
-  for (int c = 0; c < NB; ++c) a[c] = lane < NB ? A[lane * NB + c] : 0.0;
-  bool ok = true;
-  double rid = 1.0;  // lane k: 1 / L_kk
-#pragma unroll
-  for (int k = 0; k < NB; ++k) {
-    const double dkk = rdlane(a[k], k);
-    ok = ok && (dkk > 0.0);
-    // 1 / sqrt(d_kk) by v_rsq_f64 + two Newton steps and L_kk = d_kk / sqrt(d_kk): a shorter dependent chain than
-    // an IEEE square root followed by a reciprocal (wave-uniform, one per pivot)
-    const double dpos = dkk > 0.0 ? dkk : 1.0;
-    double rdk = __builtin_amdgcn_rsq(dpos);
-    rdk = rdk * fma(-0.5 * dpos * rdk, rdk, 1.5);
-    rdk = rdk * fma(-0.5 * dpos * rdk, rdk, 1.5);
-    const double dk = dpos * rdk;
-    // no masks on the updates: for lanes r <= k (and r < c) the update only touches the upper triangle
-    // a[c > r], which is never read (column k's entries L[c][k] come from lanes c > k) and is written back as zero
-    rid = (lane == k) ? rdk : rid;
-    a[k] = (lane == k) ? dk : a[k] * rdk;
-    const double lk = a[k];
-#pragma unroll
-    for (int c = k + 1; c < NB; ++c) {
-      const double lck = rdlane(a[k], c);
-      a[c] = fma(-lk, lck, a[c]);
-    }
-  }
-  KSP_WAVE_SYNC();
-  if (lane < NB) {
-#pragma unroll
-    for (int c = 0; c < NB; ++c) A[lane * NB + c] = c <= lane ? a[c] : 0.0;
-    id[lane] = rid;
-  }
-  KSP_WAVE_SYNC();
-  return ok;
-}
-
 // L Z = W (lower L in LDS, inverse diagonal id), one thread per column of the [18][ws] LDS tile W, written to
 // dst (row stride ds)
 __device__ __forceinline__ void node_forward(const double* L, const double* id, const double* W, int ws, int ncol,
@@ -1553,27 +1500,7 @@ __device__ __forceinline__ void node_forward_lean(const double* L, const double*
 }
 
 // back substitution of one 18-row node with LDS-staged operands: x = L^-T T (T row stride ts), one thread per
-// RHS column, written to out (row stride m)
-__device__ __forceinline__ void node_backsolve(const double* L, const double* id, const double* T, int ts, int m,
-                                               double* out, int tid, int nth = -1) {
-  if (nth < 0) nth = blockDim.x;
-  for (int c = tid; c < m; c += nth) {
-    double z[NB];
-#pragma unroll
-    for (int row = 0; row < NB; ++row) z[row] = T[row * ts + c];
-    // right-looking (see node_forward)
-#pragma unroll
-    for (int k = NB - 1; k >= 0; --k) {
-      z[k] *= id[k];
-#pragma unroll
-      for (int row = 0; row < k; ++row) z[row] -= L[k * NB + row] * z[k];
-    }
-#pragma unroll
-    for (int row = 0; row < NB; ++row) out[row * m + c] = z[row];
-  }
-}
-
-// node_backsolve with the L loads kept per row (see node_forward_lean)
+// RHS column, written to out (row stride m); right-looking, the L loads kept per row (see node_forward_lean)
 __device__ __forceinline__ void node_backsolve_lean(const double* L, const double* id, const double* T, int ts, int m,
                                                     double* out, int tid, int nth) {
   for (int c = tid; c < m; c += nth) {
@@ -1581,7 +1508,7 @@ __device__ __forceinline__ void node_backsolve_lean(const double* L, const doubl
 #pragma unroll
     for (int row = 0; row < NB; ++row) z[row] = T[row * ts + c];
 #pragma unroll
-    for (int k = NB - 1; k >= 0; --k) {  // the arithmetic of node_backsolve, in the same order
+    for (int k = NB - 1; k >= 0; --k) {
       asm volatile("" ::: "memory");
       z[k] *= id[k];
 #pragma unroll
@@ -1800,17 +1727,15 @@ __device__ __forceinline__ void level_products(const SpDev& d, const double* Zl,
 
 // fused level: node i (i % 2s == 0) absorbs its level-s eliminated neighbours i -+ s, then either is
 // eliminated at level 2s (Cholesky + Z_i with the couplings to i -+ 2s it computes itself), stays for the next
-// level, or -- node 0 once no partner is left -- solves X_0 = D_0^-1 R_0.
-// level_step: one node's share, by the `nth` threads of a node group (tid = the thread's index in the group); every
-// thread of the block calls it (act: the group has a node at this level), with the same three block barriers on every
-// path, so that k_sp_deep can run several groups (and several levels) in one block.  L, id and sm (Zl | Zr | W,
-// [18][wc] each) are the group's LDS (the couplings Ui, Uo are formed in W, the forward solve's operand).
-// LEAN: k_sp_deep's 1024-thread block (128 VGPRs): fewer loads in flight, per-row forward solve.  LF: only the solves
-// with per-row L loads (the first level's 501 blocks: 132 VGPRs, all resident at once, 22.7 -> 16.5 us; the hoisted
-// solves are ~2 us faster on the narrower levels, whose blocks fit in one round anyway).  Same arithmetic, same bits.
-template <bool LEAN, bool LF = LEAN>
-__device__ __forceinline__ void level_step(const SpDev& d, int s, int i, bool act, int tid, int nth, double* L,
-                                           double* id, double* sm) {
+// level, or -- node 0 once no partner is left -- is factored and leaves Z_R,0 = L_0^-1 R_0' (the top node).
+// level_step: one node's share, by the block's `nth` threads.  L, id and sm (Zl | Zr | W, [18][wc] each) are the
+// block's LDS (the couplings Ui, Uo are formed in W, the forward solve's operand).
+// LF: the solves with per-row L loads (the first level's 501 blocks: 132 VGPRs, all resident at once, 22.7 -> 16.5 us;
+// the hoisted solves are ~2 us faster on the narrower levels, whose blocks fit in one round anyway).  Same arithmetic,
+// same bits.
+template <bool LF>
+__device__ __forceinline__ void level_step(const SpDev& d, int s, int i, int tid, int nth, double* L, double* id,
+                                           double* sm) {
   const int m = d.m, wc = 36 + m;
   const int jl = i - s, jr = i + s;
   const bool hl = jl >= 0, hr = jr < d.n;
@@ -1821,11 +1746,11 @@ __device__ __forceinline__ void level_step(const SpDev& d, int s, int i, bool ac
   double* W = Zr + NB * wc;  // [Ui^T | Uo | R']
   // diagnostics: block 1 of the level (block 0 once it is alone), slots 120 + 6 lv + k (tools/diag_sp_levels.py)
   const int tsb = gridDim.x > 1 ? 1 : 0, tsl = 120 + 6 * (31 - __clz(s));
-  if (!LEAN) KSP_TSB(tsb, tsl);
-  const bool fin = act && (elim || top);
+  KSP_TSB(tsb, tsl);
+  const bool fin = elim || top;
   __shared__ int dflag;  // level_products: wave 1's D' tiles stored (reset before the first barrier)
   if (tid == 0) dflag = 0;
-  if (act) {
+  {
     // Zl | Zr | D_i (into L) | R_i (into W's R columns) in one batch of loads; absent neighbours read node i's Z
     // slot (any valid address) and store zeros
     const double* Zsl = d.Z + (size_t)(hl ? jl : i) * NB * wc;
@@ -1834,8 +1759,7 @@ __device__ __forceinline__ void level_step(const SpDev& d, int s, int i, bool ac
     const double* Ri = (s == 1 ? d.R0 : d.R) + (size_t)i * NB * m;
     const double lam2 = s == 1 ? d.sc[SC_LAM2] : 0.0;
     const int nz = NB * wc;
-    constexpr int UZ = LEAN ? 3 : 6, UD = LEAN ? 3 : 2, UR = LEAN ? 3 : 3;
-    double vl[UZ], vr[UZ], vd[UD], vq[UR];
+    double vl[6], vr[6], vd[2], vq[3];
     seg_ld(vl, Zsl, nz, tid, nth);
     seg_ld(vr, Zsr, nz, tid, nth);
     seg_ld(vd, Di, NB * NB, tid, nth);
@@ -1851,18 +1775,18 @@ __device__ __forceinline__ void level_step(const SpDev& d, int s, int i, bool ac
   }
   __syncthreads();
   KSP_STOP(1);
-  if (!LEAN) KSP_TSB(tsb, tsl + 1);
-  // (4-wave groups: a finishing node's Cholesky inside, on wave 0, behind its D' tiles)
-  const bool early = !LEAN && fin && nth == 256;
-  if (act) level_products(d, Zl, Zr, L, id, W, m, wc, tid, nth, LEAN ? -1 : tsb, early, &dflag);
+  KSP_TSB(tsb, tsl + 1);
+  // (4-wave blocks: a finishing node's Cholesky inside, on wave 0, behind its D' tiles)
+  const bool early = fin && nth == 256;
+  level_products(d, Zl, Zr, L, id, W, m, wc, tid, nth, tsb, early, &dflag);
   __syncthreads();
   KSP_STOP(2);
-  if (!LEAN) KSP_TSB(tsb, tsl + 2);
-  if (act && !fin) {  // stays active: D', R' for the next level (the coupling is recomputed from Z by both nodes)
+  KSP_TSB(tsb, tsl + 2);
+  if (!fin) {  // stays active: D', R' for the next level (the coupling is recomputed from Z by both nodes)
     for (int q = tid; q < NB * NB; q += nth) d.D[(size_t)i * NB * NB + q] = L[q];
     for (int q = tid; q < NB * m; q += nth) d.R[(size_t)i * NB * m + q] = W[(q / m) * wc + 2 * NB + q % m];
   }
-  if (LEAN || !early) {  // the Cholesky after the products (k_sp_deep's groups: the same barriers on every path)
+  if (!early) {  // the Cholesky after the products
     if (fin && tid < 64) {
       const bool ok = chol18_wave(L, id, tid);
       if (!ok && tid == 0) d.sc[SC_OK] = 0.0;
@@ -1870,28 +1794,20 @@ __device__ __forceinline__ void level_step(const SpDev& d, int s, int i, bool ac
     __syncthreads();
   }
   KSP_STOP(3);
-  if (!LEAN) KSP_TSB(tsb, tsl + 3);
-  if (fin && top && d.zs) {  // Z_R,0 = L^-1 R' and the factor: the back substitution solves x_0 with one column later
+  KSP_TSB(tsb, tsl + 3);
+  if (top) {  // Z_R,0 = L^-1 R' and the factor: the back substitution solves x_0 with one column later
     if (LF) node_forward_lean(L, id, W + 2 * NB, wc, m, d.Z + 2 * NB, wc, tid, nth);
     else node_forward(L, id, W + 2 * NB, wc, m, d.Z + 2 * NB, wc, tid, nth);
     for (int q = tid; q < NB * NB; q += nth) d.Lf[q] = L[q];
     if (tid < NB) d.Lid[tid] = id[tid];
-  } else if (fin && top) {  // X_0 = L^-T L^-1 R' (forward in place in W, then backward into X_0)
-    if (LF) {
-      node_forward_lean(L, id, W + 2 * NB, wc, m, W + 2 * NB, wc, tid, nth);
-      node_backsolve_lean(L, id, W + 2 * NB, wc, m, d.X, tid, nth);
-    } else {
-      node_forward(L, id, W + 2 * NB, wc, m, W + 2 * NB, wc, tid, nth);
-      node_backsolve(L, id, W + 2 * NB, wc, m, d.X, tid, nth);
-    }
-  } else if (fin) {
+  } else if (elim) {  // Z_i and the factor
     if (LF) node_forward_lean(L, id, W, wc, wc, d.Z + (size_t)i * NB * wc, wc, tid, nth);
     else node_forward(L, id, W, wc, wc, d.Z + (size_t)i * NB * wc, wc, tid, nth);
     KSP_STOP(4);
     for (int q = tid; q < NB * NB; q += nth) d.Lf[(size_t)i * NB * NB + q] = L[q];
     if (tid < NB) d.Lid[(size_t)i * NB + tid] = id[tid];
   }
-  if (!LEAN) KSP_TSB(tsb, tsl + 4);
+  KSP_TSB(tsb, tsl + 4);
 }
 
 __device__ __forceinline__ void zschur_block(const SpDev& d, int blk, double* sm);
@@ -1908,7 +1824,7 @@ __global__ void __launch_bounds__(256) k_sp_level(SpDev d, int s) {
   }
   const int i = 2 * s * blockIdx.x;
   if (i >= d.n) return;  // block-uniform
-  level_step<false, LF>(d, s, i, true, threadIdx.x, blockDim.x, L, id, sm);
+  level_step<LF>(d, s, i, threadIdx.x, blockDim.x, L, id, sm);
 }
 
 __global__ void __launch_bounds__(256) k_sp_top(SpDev d) {
@@ -1925,581 +1841,21 @@ __global__ void __launch_bounds__(256) k_sp_top(SpDev d) {
     if (!ok && tid == 0) d.sc[SC_OK] = 0.0;
   }
   __syncthreads();
-  if (d.zs) {  // Z_R,0 and the factor (see level_step)
-    node_forward(L, id, T, m, m, d.Z + 2 * NB, 36 + m, tid);
-    for (int q = tid; q < NB * NB; q += blockDim.x) d.Lf[q] = L[q];
-    if (tid < NB) d.Lid[tid] = id[tid];
-    return;
-  }
-  node_forward(L, id, T, m, m, T, m, tid);
-  node_backsolve(L, id, T, m, m, d.X, tid);
-}
-
-// T = Z_R - Z_Uin x_l - Z_U x_r of one node on MFMA tiles (the node group's nth threads): T[row][c] = Z_R[row][c] -
-// sum_k (Z[row][k] xl[k][c] + Z[row][NB + k] xr[k][c]); A = Z^T is read from the Z rows (stride 1 in k), B from xl / xr
-__device__ __forceinline__ void back_T(const double* Z, const double* xl, const double* xr, double* T, int m, int wc,
-                                       int tid, int nth) {
-  const int wave = tid >> 6, lane = tid & 63, nw = nth >> 6, nct = (m + 15) >> 4;
-  for (int t = wave; t < 2 * nct; t += nw) {
-    const int ti = t / nct, tj = t % nct, i = lane & 15;
-    const int rc = min(16 * ti + i, NB - 1), cc = min(16 * tj + i, m - 1);
-    const bool rv = 16 * ti + i < NB, cv = 16 * tj + i < m;
-    // operands first (see level_products), the two sides in two accumulator chains
-    double av[2][5], bv[2][5];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const double* B = h ? xr : xl;
-#pragma unroll
-      for (int st = 0; st < 5; ++st) {
-        const int kc = min(4 * st + (lane >> 4), NB - 1);
-        av[h][st] = Z[rc * wc + h * NB + kc];
-        bv[h][st] = B[kc * m + cc];
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    v4d_t ac[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
-#pragma unroll
-    for (int st = 0; st < 5; ++st) {
-      const bool kv = 4 * st + (lane >> 4) < NB;
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-        ac[h] = __builtin_amdgcn_mfma_f64_16x16x4f64((kv && rv) ? av[h][st] : 0.0, (kv && cv) ? bv[h][st] : 0.0, ac[h], 0, 0, 0);
-    }
-    const v4d_t acc = ac[0] + ac[1];
-    const int c = 16 * tj + (lane & 15);
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      const int row = 16 * ti + (lane >> 4) + 4 * rr;
-      if (row < NB && c < m) T[row * m + c] = Z[row * wc + 2 * NB + c] - acc[rr];
-    }
-  }
-}
-
-// back_step: node j's back substitution by a node group (the contract of level_step: every thread of the block
-// calls it, two block barriers on every path); L, id and sm (Z [18][wc] | xl | xr | T [18][m]) are the group's LDS
-template <bool LEAN>
-__device__ __forceinline__ void back_step(const SpDev& d, int s, int j, bool act, int tid, int nth, double* L,
-                                          double* id, double* sm) {
-  const int m = d.m, wc = 36 + m;
-  const int l = j - s, r = j + s;
-  const bool hr = r < d.n;
-  double* Z = sm;
-  double* xl = Z + NB * wc;
-  double* xr = xl + NB * m;
-  double* T = xr + NB * m;
-  const int tsl = 190 + 4 * (31 - __clz(s));
-  if (!LEAN) KSP_TSB(0, tsl);
-  if (act) {
-    // L_j | 1/diag | Z_j | x_l | x_r in one batch of loads (x_r of an absent neighbour: zeros)
-    const double* Ls = d.Lf + (size_t)j * NB * NB;
-    const double* Is = d.Lid + (size_t)j * NB;
-    const double* Zs = d.Z + (size_t)j * NB * wc;
-    const double* Xl = d.X + (size_t)l * NB * m;
-    const double* Xr = d.X + (size_t)(hr ? r : l) * NB * m;
-    constexpr int UL = 2, UZ = LEAN ? 3 : 6, UX = LEAN ? 3 : 3;
-    double vL[UL], vI[1], vZ[UZ], vxl[UX], vxr[UX];
-    seg_ld(vL, Ls, NB * NB, tid, nth);
-    seg_ld(vI, Is, NB, tid, nth);
-    seg_ld(vZ, Zs, NB * wc, tid, nth);
-    seg_ld(vxl, Xl, NB * m, tid, nth);
-    seg_ld(vxr, Xr, NB * m, tid, nth);
-    seg_st(vL, Ls, NB * NB, tid, nth, [&](int q, double v) { L[q] = v; });
-    seg_st(vI, Is, NB, tid, nth, [&](int q, double v) { id[q] = v; });
-    seg_st(vZ, Zs, NB * wc, tid, nth, [&](int q, double v) { Z[q] = v; });
-    seg_st(vxl, Xl, NB * m, tid, nth, [&](int q, double v) { xl[q] = v; });
-    seg_st(vxr, Xr, NB * m, tid, nth, [&](int q, double v) { xr[q] = hr ? v : 0.0; });
-  }
-  __syncthreads();
-  KSP_STOP(1);
-  if (!LEAN) KSP_TSB(0, tsl + 1);
-  if (act) back_T(Z, xl, xr, T, m, wc, tid, nth);
-  __syncthreads();
-  KSP_STOP(2);
-  if (!LEAN) KSP_TSB(0, tsl + 2);
-  if (act) {
-    if (LEAN) node_backsolve_lean(L, id, T, m, m, d.X + (size_t)j * NB * m, tid, nth);
-    else node_backsolve(L, id, T, m, m, d.X + (size_t)j * NB * m, tid, nth);
-  }
-  if (!LEAN) KSP_TSB(0, tsl + 3);
-}
-
-__global__ void __launch_bounds__(256) k_sp_back(SpDev d, int s) {
-  __shared__ double L[NB * NB];
-  __shared__ double id[NB];
-  extern __shared__ __attribute__((aligned(16))) double sm[];  // Z [18][wc] | xl [18][m] | xr [18][m] | T [18][m]
-  const int j = s + 2 * s * blockIdx.x;
-  if (j >= d.n) return;  // block-uniform
-  back_step<false>(d, s, j, true, threadIdx.x, blockDim.x, L, id, sm);
-}
-
-// two back-substitution levels in one launch (round 5): strides 2s and s.  Block b takes node j = s + 2sb of stride s.
-// Of its neighbours j -+ s (multiples of 2s) the odd multiple of 2s, k, belongs to stride 2s: the block solves it first
-// (x_{k -+ 2s} are known), then j from x_k (in LDS) and its other neighbour o.  x_k is solved by the blocks on both
-// sides of it from the same operands by the same instructions, so both copies are bitwise equal; the block with
-// k = j + s stores it (node k - s always exists).  One launch, one batch of operand loads and one launch gap instead
-// of two; every value is computed as by two k_sp_back launches.
-__global__ void __launch_bounds__(256) k_sp_back2(SpDev d, int s) {
-  __shared__ double L[2][NB * NB];
-  __shared__ double id[2][NB];
-  // node k: Zk [18][wc] | xa | xb [18][m]; node j: Zj [18][wc] | xjl | xjr [18][m]; T [18][m]
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  const int b = blockIdx.x, j = s + 2 * s * b, tid = threadIdx.x, nth = blockDim.x;
-  if (j >= d.n) return;  // block-uniform
-  const int tsl = 190 + 4 * (31 - __clz(s));  // diagnostics: the stride-s slots (x_k done in place of T)
-  KSP_TSB(0, tsl);
-  const int m = d.m, wc = 36 + m, n = d.n;
-  const bool kl = (b & 1) != 0;  // k = j - s (b odd) or k = j + s (b even)
-  const int k = kl ? j - s : j + s, o = kl ? j + s : j - s;
-  const bool hk = k < n, ho = o < n, hkb = k + 2 * s < n;
-  double* Zk = sm;
-  double* xa = Zk + NB * wc;
-  double* xb = xa + NB * m;
-  double* Zj = xb + NB * m;
-  double* xjl = Zj + NB * wc;
-  double* xjr = xjl + NB * m;
-  double* T = xjr + NB * m;
-  double* xk = kl ? xjl : xjr;  // x_k among node j's operands
-  double* xo = kl ? xjr : xjl;
-  {
-    // L_k | 1/diag_k | Z_k | x_{k-2s} | x_{k+2s} | L_j | 1/diag_j | Z_j | x_o in one batch (absent nodes: zeros; their
-    // loads read node j's slots)
-    const int kc = hk ? k : j;
-    const double* Lks = d.Lf + (size_t)kc * NB * NB;
-    const double* Iks = d.Lid + (size_t)kc * NB;
-    const double* Zks = d.Z + (size_t)kc * NB * wc;
-    const double* Xas = d.X + (size_t)(hk ? k - 2 * s : j - s) * NB * m;
-    const double* Xbs = d.X + (size_t)(hkb ? k + 2 * s : j - s) * NB * m;
-    const double* Ljs = d.Lf + (size_t)j * NB * NB;
-    const double* Ijs = d.Lid + (size_t)j * NB;
-    const double* Zjs = d.Z + (size_t)j * NB * wc;
-    const double* Xos = d.X + (size_t)(ho ? o : j - s) * NB * m;
-    if (!hk)
-      for (int q = tid; q < NB * m; q += nth) xk[q] = 0.0;
-    double vLk[2], vIk[1], vZk[6], vxa[3], vxb[3], vLj[2], vIj[1], vZj[6], vxo[3];
-    seg_ld(vLk, Lks, NB * NB, tid, nth);
-    seg_ld(vIk, Iks, NB, tid, nth);
-    seg_ld(vZk, Zks, NB * wc, tid, nth);
-    seg_ld(vxa, Xas, NB * m, tid, nth);
-    seg_ld(vxb, Xbs, NB * m, tid, nth);
-    seg_ld(vLj, Ljs, NB * NB, tid, nth);
-    seg_ld(vIj, Ijs, NB, tid, nth);
-    seg_ld(vZj, Zjs, NB * wc, tid, nth);
-    seg_ld(vxo, Xos, NB * m, tid, nth);
-    seg_st(vLk, Lks, NB * NB, tid, nth, [&](int q, double v) { L[0][q] = v; });
-    seg_st(vIk, Iks, NB, tid, nth, [&](int q, double v) { id[0][q] = v; });
-    seg_st(vZk, Zks, NB * wc, tid, nth, [&](int q, double v) { Zk[q] = v; });
-    seg_st(vxa, Xas, NB * m, tid, nth, [&](int q, double v) { xa[q] = v; });
-    seg_st(vxb, Xbs, NB * m, tid, nth, [&](int q, double v) { xb[q] = hkb ? v : 0.0; });
-    seg_st(vLj, Ljs, NB * NB, tid, nth, [&](int q, double v) { L[1][q] = v; });
-    seg_st(vIj, Ijs, NB, tid, nth, [&](int q, double v) { id[1][q] = v; });
-    seg_st(vZj, Zjs, NB * wc, tid, nth, [&](int q, double v) { Zj[q] = v; });
-    seg_st(vxo, Xos, NB * m, tid, nth, [&](int q, double v) { xo[q] = ho ? v : 0.0; });
-  }
-  __syncthreads();
-  KSP_TSB(0, tsl + 1);
-  if (hk) back_T(Zk, xa, xb, T, m, wc, tid, nth);  // block-uniform branches
-  __syncthreads();
-  if (hk) node_backsolve(L[0], id[0], T, m, m, xk, tid, nth);
-  __syncthreads();
-  KSP_TSB(0, tsl + 2);
-  if (hk && !kl)
-    for (int q = tid; q < NB * m; q += nth) d.X[(size_t)k * NB * m + q] = xk[q];
-  back_T(Zj, xjl, xjr, T, m, wc, tid, nth);
-  __syncthreads();
-  node_backsolve(L[1], id[1], T, m, m, d.X + (size_t)j * NB * m, tid, nth);
-  KSP_TSB(0, tsl + 3);
-}
-
-// the deep levels in one block (round 4): once a level has at most kSpDeepGroups nodes, the remaining levels down to
-// the top and back up to the same stride run in one block of kSpDeepGroups node groups of kSpDeepGT threads, a block
-// barrier between levels instead of a kernel boundary (the L2 writeback and the launch of every level, and the
-// operands come back from the CU's own cache).  Levels s_deep .. top, then the back substitution top .. s_deep.
-constexpr int kSpDeepGroups = 4;
-// LDS of one k_sp_deep node group, in doubles: L | id | Zl | Zr | W ([18][36 + m] each)
-__host__ __device__ constexpr int kSpDeepPer(int m) { return NB * NB + NB + 3 * NB * (36 + m); }
-constexpr int kSpDeepGT = 128;  // threads per node group: the block keeps the per-level kernels' 256-VGPR budget
-__global__ void __launch_bounds__(kSpDeepGT * kSpDeepGroups) k_sp_deep(SpDev d, int s_deep) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  // wave-uniform group index: the per-node branches (active, eliminated, top) are scalar branches
-  const int g = __builtin_amdgcn_readfirstlane(threadIdx.x / kSpDeepGT), tid = threadIdx.x % kSpDeepGT;
-  // the group size as an opaque value, as blockDim.x is in k_sp_level / k_sp_back: a compile-time stride lets the
-  // compiler unroll the strided output loops and hoist their operands (hundreds of spilled VGPRs)
-  int nth = kSpDeepGT;
-  asm volatile("" : "+s"(nth));
-  const int wc = 36 + d.m, per = kSpDeepPer(d.m);  // the group's LDS: L | id | Zl | Zr | W
-  double* L = sm + (size_t)g * per;
-  double* id = L + NB * NB;
-  double* gsm = id + NB;
-  int s = s_deep;
-  for (;; s *= 2) {
-    const int i = 2 * s * g;
-    level_step<true>(d, s, i, i < d.n, tid, nth, L, id, gsm);
-    __syncthreads();  // this level's D / U / R / Z / X stores before the next level's loads
-    if (2 * s >= d.n) break;
-  }
-  for (; s >= s_deep; s /= 2) {
-    const int j = s + 2 * s * g;
-    back_step<true>(d, s, j, j < d.n, tid, nth, L, id, gsm);
-    __syncthreads();
-  }
-}
-
-// ---------------------------------------------------------------- partitioned band solve (default)
-// The block-tridiagonal coefficient system solved by nested partitioning instead of cyclic reduction: the nodes of
-// a level are cut into chunks of q consecutive nodes whose last node is the chunk's separator.  One block per chunk
-// eliminates the chunk's interior nodes in order (block Thomas: Cholesky of the node, Z = L^-1 [U_j | F_j | R_j],
-// the next node's D, its fill coupling F to the left separator and its right-hand side updated by Z_U^T Z), which
-// leaves a block-tridiagonal system over the separators (level l + 1: P = ceil(n / q) nodes).  The levels repeat
-// until at most kSpTop nodes remain; one block solves that system by the same elimination and a back-substitution
-// sweep, and the back kernels walk the levels down again (x_j = L_j^-T (Z_R - Z_U x_{j+1} - Z_F x_sepL)).
-//   configs[4]: n = 1001 -> 63 (q = 16) -> 8 (q = 8) -> top: 5 launches whose dependent chain is 15 + 7 + 8
-//   eliminations and 8 + 7 + 15 substitution steps, instead of 21 launches of one cyclic-reduction level each.
-// Level l's system: D_i = Dt_i + Dh_i (the separator's own chunk / the next chunk's elimination; Dh of the last
-// node is absent), U_i (block (i, i + 1)), R_i = Rt_i + Rh_i.  Level 0 reads the built blocks D0 + lambda^2 I, U0, R0.
-constexpr int kSpTop = 16;  // largest system the one-block top kernel solves
-constexpr int kSpWc = 36 + MAXC + 1;  // LDS row stride of [U | F | R] (m <= MAXC + 1)
-
-struct SpLvl {
-  int n, q, lvl;                          // nodes, chunk length (interior nodes + the separator), level
-  const double *Dt, *Dh, *U, *Rt, *Rh;    // this level's system (lvl 0: D0, -, U0, R0, -)
-  double *Lf, *Lid, *Z, *X;               // factors [n][324], [n][18], [n][18][36 + m]; solution [n][18][m]
-  double *nDt, *nDh, *nU, *nRt, *nRh;     // chunk kernel: the next level's system
-  const double* Xup;                      // back kernel: the next level's solution
-};
-
-// raw entry e of node i's [D (324) | U (324) | R (18 m)] at level L
-__device__ __forceinline__ double lvl_raw(const SpDev& d, const SpLvl& L, int i, int e, double lam2) {
-  const int m = d.m;
-  const bool nx = i + 1 < L.n;
-  if (e < NB * NB) {
-    const size_t o = (size_t)i * NB * NB + e;
-    return L.lvl == 0 ? L.Dt[o] + lam_diag(d, i, e, lam2) : L.Dt[o] + (nx ? L.Dh[o] : 0.0);
-  }
-  if (e < 2 * NB * NB) return L.U[(size_t)i * NB * NB + e - NB * NB];
-  const size_t o = (size_t)i * NB * m + e - 2 * NB * NB;
-  return L.lvl == 0 ? L.Rt[o] : L.Rt[o] + (nx ? L.Rh[o] : 0.0);
-}
-
-constexpr int kSpRawU = (2 * NB * NB + NB * (MAXC + 1) + 255) / 256;  // raw items per thread (256 threads)
-
-// the node update of chunk_forward on f64 MFMA tiles (see there); U tiles: rows = the 18 Z_U columns, columns =
-// [U | F | R] (D~, F, R~ of the next node); F tiles (hasL): rows = the Z_F columns, columns = [F | R] (Dh, Rh)
-__device__ __forceinline__ void chunk_update_mfma(const double* Zs, int wc, int m, const double* Raw, double* Lc,
-                                                  double* W, double* Dh, double* Rh, bool hasL, int tid) {
-  const int wave = tid >> 6, lane = tid & 63, li = lane & 15, kq = lane >> 4;
-  const int nct_u = (36 + m + 15) >> 4, nct_f = (NB + m + 15) >> 4;
-  const int nt_u = 2 * nct_u, nt = nt_u + (hasL ? 2 * nct_f : 0);
-  for (int t = wave; t < nt; t += 4) {
-    const bool fu = t >= nt_u;
-    const int tt = fu ? t - nt_u : t, nct = fu ? nct_f : nct_u;
-    const int ti = tt / nct, tj = tt - ti * nct;
-    const int ca = fu ? NB : 0, ncb = fu ? NB + m : 36 + m;
-    const int arc = min(16 * ti + li, NB - 1), bcc = min(16 * tj + li, ncb - 1);
-    v4d_t acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int st = 0; st < 5; ++st) {
-      const int k = 4 * st + kq, kc = min(k, NB - 1);
-      const double av = Zs[kc * wc + ca + arc], bv = Zs[kc * wc + ca + bcc];
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(k < NB ? av : 0.0, bv, acc, 0, 0, 0);
-    }
-    const int c = 16 * tj + li;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int a = 16 * ti + kq + 4 * r;
-      if (a < NB && c < ncb) {
-        const double val = acc[r];
-        if (!fu) {
-          if (c < NB) Lc[a * NB + c] = Raw[a * NB + c] - val;
-          else if (c < 2 * NB) W[a * wc + c] = -val;
-          else W[a * wc + c] = Raw[2 * NB * NB + a * m + c - 2 * NB] - val;
-        } else {
-          if (c < NB) Dh[a * NB + c] -= val;
-          else Rh[a * m + c - NB] -= val;
-        }
-      }
-    }
-  }
-  for (int q = tid; q < NB * NB; q += 256) W[(q / NB) * wc + q % NB] = Raw[NB * NB + q];  // U of node j + 1: raw
-}
-
-// forward elimination of nodes a .. e - 1 of one chunk (e = its separator; sepL = a - 1 when hasL) by one 256-thread
-// block.  On return Lc holds D~_e (whole), W = [U_e raw | F_e | R~_e], Dh / Rh the left separator's accumulated
-// updates (hasL).  Writes L_j, 1/diag, Z_j of every interior node.  Returns false if a node block is not PD.
-__device__ bool chunk_forward(const SpDev& d, const SpLvl& L, int a, int e, bool hasL, double lam2, double* Lc,
-                              double* idc, double* W, double* Zs, double* Dh, double* Rh, double* Raw) {
-  const int tid = threadIdx.x, m = d.m, wc = 36 + m, nraw = 2 * NB * NB + NB * m;
-  bool ok = true;
-  // node a: D -> Lc, U -> W[:, 0:18], U_{a-1}^T -> W[:, 18:36] (block (a, a-1)), R -> W[:, 36:]
-  double v[kSpRawU];
-#pragma unroll
-  for (int u = 0; u < kSpRawU; ++u) v[u] = lvl_raw(d, L, a, min(tid + 256 * u, nraw - 1), lam2);
-  double fl[2];
-  const int ua = hasL ? a - 1 : a;
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int q = min(tid + 256 * u, NB * NB - 1), r = q / NB, c = q % NB;
-    fl[u] = L.U[(size_t)ua * NB * NB + c * NB + r];
-  }
-#pragma unroll
-  for (int u = 0; u < kSpRawU; ++u) {
-    const int q = tid + 256 * u;
-    if (q < NB * NB) Lc[q] = v[u];
-    else if (q < 2 * NB * NB) W[((q - NB * NB) / NB) * wc + (q - NB * NB) % NB] = v[u];
-    else if (q < nraw) W[((q - 2 * NB * NB) / m) * wc + 36 + (q - 2 * NB * NB) % m] = v[u];
-  }
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int q = tid + 256 * u;
-    if (q < NB * NB) W[(q / NB) * wc + NB + q % NB] = hasL ? fl[u] : 0.0;
-  }
-  for (int q = tid; q < NB * NB + NB * m; q += 256) {
-    if (q < NB * NB) Dh[q] = 0.0;
-    else Rh[q - NB * NB] = 0.0;
-  }
-  // node a + 1's raw blocks in flight
-#pragma unroll
-  for (int u = 0; u < kSpRawU; ++u) v[u] = lvl_raw(d, L, min(a + 1, e), min(tid + 256 * u, nraw - 1), lam2);
-  KSP_TS(100 + L.lvl);
-  for (int j = a; j < e; ++j) {
-    __syncthreads();  // Lc, W of node j complete; the previous update's Raw reads done
-    const int ts = 4 * (j - a) + 64 * L.lvl;
-    if (j - a < 12) KSP_TS(ts);
-    // node j + 1's raw blocks to LDS (their loads went out during the previous step): no registers held across the
-    // factorisation and the forward solve
-#pragma unroll
-    for (int u = 0; u < kSpRawU; ++u)
-      if (tid + 256 * u < nraw) Raw[tid + 256 * u] = v[u];
-    if (tid < 64) {
-      const bool okj = chol18_wave(Lc, idc, tid);
-      ok = ok && okj;
-    }
-    __syncthreads();
-    if (j - a < 12) KSP_TS(ts + 1);
-    node_forward_lean(Lc, idc, W, wc, wc, Zs, wc, tid);  // Z = L^-1 [U | F | R]
-    double* Lg = L.Lf + (size_t)j * NB * NB;
-    for (int q = tid; q < NB * NB; q += 256) Lg[q] = Lc[q];
-    if (tid < NB) L.Lid[(size_t)j * NB + tid] = idc[tid];
-    __syncthreads();  // Zs complete; Lc, W free
-    if (j - a < 12) KSP_TS(ts + 2);
-    // node j + 2's raw blocks in flight while node j + 1's are consumed
-    const int jn = min(j + 2, e);
-#pragma unroll
-    for (int u = 0; u < kSpRawU; ++u) v[u] = lvl_raw(d, L, jn, min(tid + 256 * u, nraw - 1), lam2);
-    double* Zg = L.Z + (size_t)j * NB * wc;
-    for (int q = tid; q < NB * wc; q += 256) Zg[q] = Zs[q];
-    // node j + 1: D~ = D - Z_U^T Z_U -> Lc, W = [U raw | -Z_U^T Z_F | R - Z_U^T Z_R]; the left separator (hasL):
-    // Dh -= Z_F^T Z_F, Rh -= Z_F^T Z_R.  The Z^T products on f64 MFMA tiles (out[a][c] = sum_k Zs[k][ca + a]
-    // Zs[k][cb + c], k < 18 in 5 steps of 4), tiles dealt round-robin to the 4 waves
-    chunk_update_mfma(Zs, wc, m, Raw, Lc, W, Dh, Rh, hasL, tid);
-    if (j - a < 12) KSP_TS(ts + 3);
-  }
-  if (a == e) {  // no interior node: the separator's raw blocks
-#pragma unroll
-    for (int u = 0; u < kSpRawU; ++u) {
-      const int q = tid + 256 * u;
-      if (q < NB * NB) Lc[q] = v[u];
-      else if (q < 2 * NB * NB) W[((q - NB * NB) / NB) * wc + (q - NB * NB) % NB] = v[u];
-      else if (q < nraw) W[((q - 2 * NB * NB) / m) * wc + 36 + (q - 2 * NB * NB) % m] = v[u];
-    }
-  }
-  __syncthreads();
-  return ok;
-}
-
-// one block per chunk of level L: eliminate the interior, write the separators' system for level L + 1
-__global__ void __launch_bounds__(256) k_sp_chunk(SpDev d, SpLvl L) {
-  __shared__ double Lc[NB * NB], idc[NB], Dh[NB * NB];
-  __shared__ __attribute__((aligned(16))) double W[NB * kSpWc], Zs[NB * kSpWc], Rh[NB * (MAXC + 1)],
-      Raw[2 * NB * NB + NB * (MAXC + 1)];
-  const int p = blockIdx.x, tid = threadIdx.x, m = d.m, wc = 36 + m;
-  const int a = p * L.q, e = min(L.n, a + L.q) - 1;
-  const bool hasL = p > 0;
-  const double lam2 = L.lvl == 0 ? d.sc[SC_LAM2] : 0.0;
-  const bool ok = chunk_forward(d, L, a, e, hasL, lam2, Lc, idc, W, Zs, Dh, Rh, Raw);
-  if (tid == 0 && !ok) d.sc[SC_OK] = 0.0;
-  // separator p of level L + 1: Dt = D~_e, Rt = R~_e; the left separator: U_{p-1} = F_e^T, Dh_{p-1}, Rh_{p-1}
-  for (int q = tid; q < NB * NB; q += 256) {
-    L.nDt[(size_t)p * NB * NB + q] = Lc[q];
-    if (hasL) {
-      const int r = q / NB, c = q % NB;
-      L.nU[(size_t)(p - 1) * NB * NB + q] = W[c * wc + NB + r];
-      L.nDh[(size_t)(p - 1) * NB * NB + q] = Dh[q];
-    }
-  }
-  for (int q = tid; q < NB * m; q += 256) {
-    L.nRt[(size_t)p * NB * m + q] = W[(q / m) * wc + 36 + q % m];
-    if (hasL) L.nRh[(size_t)(p - 1) * NB * m + q] = Rh[q];
-  }
-}
-
-// x_j = L_j^-T (Z_R - Z_U x_{j+1} - Z_F xl) for j = e - 1 down to a, x_e given (LDS xs); the node operands of the
-// next step in flight during each step.  X rows [18][m] of each node written to L.X.
-__device__ void chunk_back(const SpDev& d, const SpLvl& L, int a, int e, bool hasL, double* Ls, double* ids,
-                           double* Zs, double* xs, double* xl, double* T) {
-  const int tid = threadIdx.x, m = d.m, wc = 36 + m, nop = NB * NB + NB + NB * wc;
-  constexpr int U = (NB * NB + NB + NB * kSpWc + 255) / 256;
-  double v[U];
-  auto load = [&](int j) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int q = min(tid + 256 * u, nop - 1);
-      v[u] = q < NB * NB ? L.Lf[(size_t)j * NB * NB + q]
-             : q < NB * NB + NB ? L.Lid[(size_t)j * NB + q - NB * NB]
-                                : L.Z[(size_t)j * NB * wc + q - NB * NB - NB];
-    }
-  };
-  if (e > a) load(e - 1);
-  KSP_TS(104 + L.lvl);
-  for (int j = e - 1; j >= a; --j) {
-    __syncthreads();  // xs = x_{j+1} complete; the previous step's Ls / Zs reads done
-    const int tb = 200 + 3 * (e - 1 - j);
-    if (L.lvl == 0 && e - 1 - j < 12) KSP_TS(tb);
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int q = tid + 256 * u;
-      if (q < NB * NB) Ls[q] = v[u];
-      else if (q < NB * NB + NB) ids[q - NB * NB] = v[u];
-      else if (q < nop) Zs[q - NB * NB - NB] = v[u];
-    }
-    if (j > a) load(j - 1);
-    __syncthreads();
-    {
-      // T = Z_R - [Z_U | Z_F] [x_{j+1}; xl] on f64 MFMA tiles (K = 18, or 36 with the left separator)
-      const int wave = tid >> 6, lane = tid & 63, li = lane & 15, kq = lane >> 4, nct = (m + 15) >> 4;
-      const int nst = hasL ? 9 : 5;
-      for (int t = wave; t < 2 * nct; t += 4) {
-        const int ti = t / nct, tj = t - ti * nct;
-        const int arc = min(16 * ti + li, NB - 1), bcc = min(16 * tj + li, m - 1);
-        v4d_t acc = {0.0, 0.0, 0.0, 0.0};
-        for (int st = 0; st < nst; ++st) {
-          const int k = 4 * st + kq;
-          const bool kv = hasL ? k < 2 * NB : k < NB;
-          const int kc = min(k, 2 * NB - 1);
-          const double av = Zs[arc * wc + kc];
-          const double bv = kc < NB ? xs[kc * m + bcc] : xl[(kc - NB) * m + bcc];
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(kv ? av : 0.0, bv, acc, 0, 0, 0);
-        }
-        const int c = 16 * tj + li;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int a = 16 * ti + kq + 4 * r;
-          if (a < NB && c < m) T[a * m + c] = Zs[a * wc + 36 + c] - acc[r];
-        }
-      }
-    }
-    __syncthreads();
-    if (L.lvl == 0 && e - 1 - j < 12) KSP_TS(tb + 1);
-    node_backsolve(Ls, ids, T, m, m, xs, tid);  // x_j replaces x_{j+1}
-    __syncthreads();
-    if (L.lvl == 0 && e - 1 - j < 12) KSP_TS(tb + 2);
-    double* Xg = L.X + (size_t)j * NB * m;
-    for (int q = tid; q < NB * m; q += 256) Xg[q] = xs[q];
-  }
-}
-
-// one block: the whole top-level system (n <= kSpTop) by elimination, the last node's solve and back-substitution
-__global__ void __launch_bounds__(256) k_sp_ctop(SpDev d, SpLvl L) {
-  __shared__ double Lc[NB * NB], idc[NB], Dh[NB * NB];
-  __shared__ __attribute__((aligned(16))) double W[NB * kSpWc], Zs[NB * kSpWc], Rh[NB * (MAXC + 1)],
-      Raw[2 * NB * NB + NB * (MAXC + 1)];
-  double* T = Raw;  // the back-substitution's T (Raw is free once the elimination is done)
-  const int tid = threadIdx.x, m = d.m, wc = 36 + m, e = L.n - 1;
-  const double lam2 = L.lvl == 0 ? d.sc[SC_LAM2] : 0.0;
-  bool ok = chunk_forward(d, L, 0, e, false, lam2, Lc, idc, W, Zs, Dh, Rh, Raw);
-  if (tid < 64) {
-    const bool okj = chol18_wave(Lc, idc, tid);
-    ok = ok && okj;
-  }
-  if (tid == 0 && !ok) d.sc[SC_OK] = 0.0;
-  __syncthreads();
-  // x_e = L^-T L^-1 R~_e (forward in place in W's R columns, backward into Rh as the x_{j+1} buffer)
-  node_forward_lean(Lc, idc, W + 36, wc, m, W + 36, wc, tid);
-  __syncthreads();
-  node_backsolve(Lc, idc, W + 36, wc, m, Rh, tid);
-  __syncthreads();
-  for (int q = tid; q < NB * m; q += 256) L.X[(size_t)e * NB * m + q] = Rh[q];
-  chunk_back(d, L, 0, e, false, Lc, idc, Zs, Rh, W, T);
-}
-
-// one block per chunk of level L: x of the separator and the left separator from level L + 1, then the interior
-__global__ void __launch_bounds__(256) k_sp_cback(SpDev d, SpLvl L) {
-  __shared__ double Ls[NB * NB], ids[NB];
-  __shared__ __attribute__((aligned(16))) double Zs[NB * kSpWc], xs[NB * (MAXC + 1)], xl[NB * (MAXC + 1)],
-      T[NB * (MAXC + 1)];
-  const int p = blockIdx.x, tid = threadIdx.x, m = d.m;
-  const int a = p * L.q, e = min(L.n, a + L.q) - 1;
-  const bool hasL = p > 0;
-  for (int q = tid; q < NB * m; q += 256) {
-    const double x = L.Xup[(size_t)p * NB * m + q];
-    xs[q] = x;
-    L.X[(size_t)e * NB * m + q] = x;
-    xl[q] = hasL ? L.Xup[(size_t)(p - 1) * NB * m + q] : 0.0;
-  }
-  chunk_back(d, L, a, e, hasL, Ls, ids, Zs, xs, xl, T);
+  // Z_R,0 and the factor (see level_step)
+  node_forward(L, id, T, m, m, d.Z + 2 * NB, 36 + m, tid);
+  for (int q = tid; q < NB * NB; q += blockDim.x) d.Lf[q] = L[q];
+  if (tid < NB) d.Lid[tid] = id[tid];
 }
 
 // ---------------------------------------------------------------- Schur complement onto theta
-// partial rows of sum_i R0_i^T X_i over NPB nodes: upper C x C | C (the g column)
-__global__ void __launch_bounds__(256) k_sp_schur(SpDev d) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];  // R0 [18][m] | X [18][m]
-  const int tid = threadIdx.x, m = d.m;
-  double* Rl = sm;
-  double* Xl = sm + NB * m;
-  double* acc = Xl + NB * m;  // [Ws]
-  short2* tab = (short2*)(acc + d.Ws);  // [Ws] (a, b) of the entries, read for every node
-  for (int q = tid; q < d.Ws; q += blockDim.x) {
-    acc[q] = 0.0;
-    tab[q] = d.uab[q];
-  }
-  const int i0 = blockIdx.x * NPB, i1 = min(d.n, i0 + NPB);
-  // node i + 1's R0 | X rows are loaded into registers while node i's products run (2 * 18 * m <= SCH_U * 256 for
-  // m = C + 1 <= MAXC + 1; launched with 256 threads)
-  constexpr int SCH_U = (2 * NB * (MAXC + 1) + 255) / 256;
-  const int nq = 2 * NB * m;
-  double v[SCH_U];
-  auto load = [&](int i) {
-    const double* R0 = d.R0 + (size_t)i * NB * m;
-    const double* X = d.X + (size_t)i * NB * m;
-#pragma unroll
-    for (int u = 0; u < SCH_U; ++u) {
-      const int q = min(tid + u * 256, nq - 1);
-      v[u] = q < NB * m ? R0[q] : X[q - NB * m];
-    }
-  };
-  if (i0 < i1) load(i0);
-  for (int i = i0; i < i1; ++i) {
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < SCH_U; ++u) {
-      const int q = tid + u * 256;
-      if (q < NB * m)
-        Rl[q] = v[u];
-      else if (q < nq)
-        Xl[q - NB * m] = v[u];
-    }
-    __syncthreads();
-    if (i + 1 < i1) load(i + 1);
-    for (int q = tid; q < d.Ws; q += blockDim.x) {
-      const short2 ab = tab[q];
-      const int a = ab.x, b = ab.y;
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < NB; ++k) s += Rl[k * m + a] * Xl[k * m + b];
-      acc[q] += s;
-    }
-  }
-  __syncthreads();
-  for (int q = tid; q < d.Ws; q += blockDim.x) d.spart[(size_t)blockIdx.x * d.Ws + q] = acc[q];
-}
-
-// zs: the camera-block partial sums of sum_i Z_R,i^T Z_R,i (Z_R,i = L_i^-1 R_i', the right-hand-side part of node i's
-// elimination at any level, the top node's included) = R0^T D^-1 R0 of k_sp_schur's sum_i R0_i^T X_i, from the forward
-// reduction alone; same blocks of NPB nodes, same entry table and k_sp_schur_red
+// the camera-block partial sums of sum_i Z_R,i^T Z_R,i (Z_R,i = L_i^-1 R_i', the right-hand-side part of node i's
+// elimination at any level, the top node's included) = R0^T D^-1 R0, from the forward reduction alone: partial rows
+// over blocks of NPB nodes (upper C x C | C, the g column), summed by k_sp_schur_red
 __device__ __forceinline__ void zschur_block(const SpDev& d, int blk, double* sm) {
-  // sm: Z_R [18][m] | acc [Ws] | tab
+  // sm: Z_R [18][m] | (unused [18][m]) | acc [Ws] | tab
   const int tid = threadIdx.x, m = d.m, wc = 36 + m;
   double* Zl = sm;
-  double* acc = sm + 2 * NB * m;  // (k_sp_schur's layout: the LDS size is the host's lds_schur)
+  double* acc = sm + 2 * NB * m;  // (the LDS size is the host's lds_schur)
   short2* tab = (short2*)(acc + d.Ws);
   for (int q = tid; q < d.Ws; q += blockDim.x) {
     acc[q] = 0.0;
@@ -2546,8 +1902,8 @@ __global__ void __launch_bounds__(256) k_sp_zschur(SpDev d) {
   zschur_block(d, blockIdx.x, sm);
 }
 
-// zs, step 1 (every node at once, after the camera solve): with v = [-dtheta | 1], node j's operands of the
-// one-column back substitution, [M_l | M_r | u] = L_j^-T [Z_Uin,j | Z_U,j | Z_R,j v] (18 x 37, row-major into bm):
+// back substitution, step 1 (every node at once, after the camera solve): with v = [-dtheta | 1], node j's operands
+// of the one-column back substitution, [M_l | M_r | u] = L_j^-T [Z_Uin,j | Z_U,j | Z_R,j v] (18 x 37, row-major into bm):
 // the chain of strides then needs no triangular solve, x_j = u_j - M_l x_{j-s} - M_r x_{j+s}
 __global__ void __launch_bounds__(256) k_sp_bprep(SpDev d) {
   // one wave per node (4 per block), wave-local LDS: L | 1/diag | T = [Z_Uin | Z_U | y] (18 x 37) | y partials | v
@@ -2612,9 +1968,9 @@ __global__ void __launch_bounds__(256) k_sp_bprep(SpDev d) {
   KSP_TSB(100, 275);
 }
 
-// zs, step 2: node j of stride s on one wave (s = 0: the top node, x_0 = u_0): lane r < 18 forms row r of
-// x_j = u_j - M_l x_{j-s} - M_r x_{j+s} (every load in one round), written to xs and as the node's coefficient steps
-// into dx
+// back substitution, step 2: node j of stride s on one wave (s = 0: the top node, x_0 = u_0): lane r < 18 forms row r
+// of x_j = u_j - M_l x_{j-s} - M_r x_{j+s} (every load in one round), written to xs and as the node's coefficient
+// steps into dx
 __device__ __forceinline__ void bvec_node(const SpDev& d, int j, int s, int lane) {
   const int C = d.C;
   const int l = j - s, r = j + s;
@@ -2641,7 +1997,7 @@ __device__ __forceinline__ void bvec_node(const SpDev& d, int j, int s, int lane
   }
 }
 
-// zs, step 2 for the deep strides in one block of 8 waves: the top node, then strides s_hi .. s_lo (at most 16 nodes
+// step 2 for the deep strides in one block of 8 waves: the top node, then strides s_hi .. s_lo (at most 16 nodes
 // each, one or two per wave), a block barrier between strides (the xs stores are block-visible after it)
 constexpr int kBvecDeepWaves = 8;
 __global__ void __launch_bounds__(64 * kBvecDeepWaves) k_sp_bvec_deep(SpDev d, int s_hi, int s_lo) {
@@ -2658,7 +2014,7 @@ __global__ void __launch_bounds__(64 * kBvecDeepWaves) k_sp_bvec_deep(SpDev d, i
   }
 }
 
-// zs, step 2 for one wider stride s: one node per wave (4 per block)
+// step 2 for one wider stride s: one node per wave (4 per block)
 __global__ void __launch_bounds__(256) k_sp_bvec(SpDev d, int s) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int j = s + 2 * s * (4 * blockIdx.x + wave);
@@ -2666,7 +2022,7 @@ __global__ void __launch_bounds__(256) k_sp_bvec(SpDev d, int s) {
   bvec_node(d, j, s, lane);
 }
 
-// S = H_cc + lam2 I - sum_i R0_i^T X_i, b = g_c - sum (4-wave interleaved partial sums), written full
+// S = H_cc + lam2 I - sum_i Z_R,i^T Z_R,i, b = g_c - sum (4-wave interleaved partial sums), written full
 __global__ void __launch_bounds__(64 * RW) k_sp_schur_red(SpDev d) {
   __shared__ double red[RW][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, C = d.C, nup = C * (C + 1) / 2;
@@ -2738,25 +2094,16 @@ __global__ void __launch_bounds__(64) k_sp_camsolve(SpDev d) {
   if (lane == 0 && !ok) d.sc[SC_OK] = 0.0;
 }
 
-// coefficient steps ds_i = X_i[:, C] - X_i[:, :C] dtheta; with `apply` (and a successful solve) the state
-// update: backup copy, additive coefficients, theta DVs (block 0); per-block max |dx|.
+// with `apply` (and a successful solve) the state update by the step in dx: backup copy, additive coefficients, theta
+// DVs (block 0); per-block max |dx|.
 __global__ void __launch_bounds__(64) k_sp_update(SpDev d, int apply) {
-  const int i = blockIdx.x, tid = threadIdx.x, C = d.C, m = d.m;
+  const int i = blockIdx.x, tid = threadIdx.x, C = d.C;
   const bool go = apply && d.sc[SC_OK] != 0.0;
   double mx = 0.0;
   if (tid < NB) {
     const int k = SB * i + tid / 6;
     if (k < d.K) {
-      double v;
-      if (d.zs) {  // written by the one-column back substitution (k_sp_bvec*)
-        v = d.dx[C + 6 * k + tid % 6];
-      } else {
-        const double* x = d.X + (size_t)i * NB * m + tid * m;
-        v = x[C];
-#pragma unroll 16
-        for (int c = 0; c < C; ++c) v -= x[c] * d.dx[c];
-        d.dx[C + 6 * k + tid % 6] = v;
-      }
+      const double v = d.dx[C + 6 * k + tid % 6];  // written by the one-column back substitution (k_sp_bvec*)
       mx = fabs(v);
       const int o = d.off_coef + 6 * k + tid % 6;
       if (go) {
@@ -3037,7 +2384,7 @@ __global__ void k_sp_set_lam(SpDev d, double lam2) {
 }
 
 // ---------------------------------------------------------------- covariance query
-// Blocks of (H + lam2 I)^-1 from the factors a zs solve leaves in HBM, by the selected inverse (Takahashi) over the
+// Blocks of (H + lam2 I)^-1 from the factors the solve leaves in HBM, by the selected inverse (Takahashi) over the
 // device's elimination order: odd multiples of s = 1, 2, 4, .., node 0, theta.  With N = (l = j - s, r = j + s, theta)
 // the neighbours of node j at its elimination, P_j = L_j^-T L_j^-1 and E_j = L_j^-T [Z_Uin | Z_U | Z_R[:, :C]]:
 //   Sigma_tt = S^-1,  Sigma_j,N = -E_j Sigma_NN,  Sigma_jj = P_j + E_j Sigma_NN E_j^T
@@ -3471,8 +2818,7 @@ struct kb_sp_handle {
   std::vector<void*> allocs;
   double lambda = 0.0;
   bool uploaded = false, built = false, solved = false;
-  size_t lds_frames = 0, lds_asm = 0, lds_elim = 0, lds_level = 0, lds_schur = 0, lds_back = 0, lds_back2 = 0;
-  bool back2 = true;       // k_sp_back2: two back-substitution strides per launch
+  size_t lds_frames = 0, lds_asm = 0, lds_elim = 0, lds_level = 0, lds_schur = 0;
   // the launched instantiations: [0] of an unweighted handle, [1] of a weighted one (pick_weighted)
   const void* fn_frames = nullptr;
   const void* fn_cost = nullptr;
@@ -3483,12 +2829,7 @@ struct kb_sp_handle {
   const void* fn_camsolve = nullptr;
   hipGraphExec_t gn_graph = nullptr;
   int gn_graph_n = 0;
-  std::vector<SpLvl> lv;  // partitioned band solve: lv[0 .. nl) chunk levels, lv[nl] the top system
-  bool use_cr = true;     // block cyclic reduction; KSP_PARTITION=1: the partitioned band solve
-  int s_deep = 0;         // first stride run by k_sp_deep (0: one launch per level)
-  int s_top = 0;          // zs: the stride the forward reduction ended at (the top node solved there)
-  int deep_groups = 0;    // k_sp_deep's node groups (kSpDeepGT threads each)
-  size_t lds_deep = 0;
+  int s_top = 0;          // the stride the forward reduction ended at (the top node solved there)
   std::vector<double> trace;
   double* host_sc = nullptr;  // pinned scalars
   // covariance query: buffers and launch sizes made by the first kb_sp_covariance / kb_sp_curve_covariance
@@ -3573,21 +2914,10 @@ int launch_build(kb_sp_handle* h) {
   return 0;
 }
 
+// the forward half of the cyclic reduction (every node's factor and Z); the back substitution runs after the camera
+// solve, with one column (launch_bvec)
 int launch_reduction(kb_sp_handle* h) {
   SpDev& d = h->d;
-  if (!h->use_cr) {  // partitioned: chunk levels down, the top system, back-substitution levels up
-    const int nl = (int)h->lv.size() - 1;
-    for (int l = 0; l < nl; ++l) {
-      const SpLvl& L = h->lv[l];
-      hipLaunchKernelGGL(k_sp_chunk, dim3((L.n + L.q - 1) / L.q), dim3(256), 0, h->stream, d, L);
-    }
-    hipLaunchKernelGGL(k_sp_ctop, dim3(1), dim3(256), 0, h->stream, d, h->lv[nl]);
-    for (int l = nl - 1; l >= 0; --l) {
-      const SpLvl& L = h->lv[l];
-      hipLaunchKernelGGL(k_sp_cback, dim3((L.n + L.q - 1) / L.q), dim3(256), 0, h->stream, d, L);
-    }
-    return 0;
-  }
   if (d.n == 1) {
     hipLaunchKernelGGL(k_sp_top, dim3(1), dim3(256), sizeof(double) * NB * d.m, h->stream, d);
     h->s_top = 1;
@@ -3595,41 +2925,17 @@ int launch_reduction(kb_sp_handle* h) {
   }
   hipLaunchKernelGGL(k_sp_elim1, dim3(d.n / 2 + (d.cc_fused ? (d.Wc + 3) / 4 : 0)), dim3(256), h->lds_elim, h->stream, d);
   int s = 1;
-  const int sd = h->s_deep;
-  for (; s < d.n && !(sd && s >= sd); s *= 2) {
+  for (; s < d.n; s *= 2) {
     const bool last = d.zsf && 2 * s >= d.n;  // the top level: one block, the Schur sums beside it
     hipLaunchKernelGGL(s == 1 ? k_sp_level<true> : k_sp_level<false>,
                        dim3((d.n + 2 * s - 1) / (2 * s) + (last ? d.nblk_s : 0)), dim3(256),
                        last ? std::max(h->lds_level, h->lds_schur) : h->lds_level, h->stream, d, s);
   }
-  if (d.zs) {  // the back substitution runs after the camera solve, with one column (launch_bvec)
-    h->s_top = s;
-    return 0;
-  }
-  if (sd && s < d.n) {  // the remaining levels down and back up to stride sd in one block
-    hipLaunchKernelGGL(k_sp_deep, dim3(1), dim3(kSpDeepGT * h->deep_groups), h->lds_deep, h->stream, d, sd);
-    s = sd;
-  }
-  // back-substitution strides s/2 .. 1: with k_sp_back2 two per launch (an odd count leaves the top one single)
-  int nb = 0;
-  for (int t = s / 2; t >= 1; t /= 2) ++nb;
-  for (s /= 2; s >= 1;) {
-    if (h->back2 && (nb & 1) == 0) {
-      const int sl = s / 2, ne = (d.n - sl + 2 * sl - 1) / (2 * sl);
-      hipLaunchKernelGGL(k_sp_back2, dim3(ne), dim3(256), h->lds_back2, h->stream, d, sl);
-      s /= 4;
-      nb -= 2;
-    } else {
-      const int ne = (d.n - s + 2 * s - 1) / (2 * s);
-      hipLaunchKernelGGL(k_sp_back, dim3(ne), dim3(256), h->lds_back, h->stream, d, s);
-      s /= 2;
-      nb -= 1;
-    }
-  }
+  h->s_top = s;
   return 0;
 }
 
-// zs: the back substitution with v = [-dtheta | 1]: the top node and the strides with at most 16 nodes in one block
+// the back substitution with v = [-dtheta | 1]: the top node and the strides with at most 16 nodes in one block
 // (k_sp_bvec_deep), the wider strides one launch each (a wave per node)
 int launch_bvec(kb_sp_handle* h) {
   SpDev& d = h->d;
@@ -3647,11 +2953,10 @@ int launch_solve(kb_sp_handle* h) {
   SpDev& d = h->d;
   void* args[] = {&d};
   launch_reduction(h);
-  if (!d.zsf) hipLaunchKernelGGL(d.zs ? k_sp_zschur : k_sp_schur, dim3(d.nblk_s), dim3(256), h->lds_schur, h->stream, d);
+  if (!d.zsf) hipLaunchKernelGGL(k_sp_zschur, dim3(d.nblk_s), dim3(256), h->lds_schur, h->stream, d);
   hipLaunchKernelGGL(k_sp_schur_red, dim3((d.Ws + 63) / 64), dim3(64 * RW), 0, h->stream, d);
   KSP_HIP(hipLaunchKernel(h->fn_camsolve, dim3(1), dim3(64), args, 0, h->stream));
-  if (d.zs) return launch_bvec(h);
-  return 0;
+  return launch_bvec(h);
 }
 
 int launch_cost(kb_sp_handle* h, int with_dx) {
@@ -3668,8 +2973,8 @@ int launch_cost(kb_sp_handle* h, int with_dx) {
 int enqueue_gn_pass(kb_sp_handle* h) {
   SpDev& d = h->d;
   d.zero_lam = 1;  // lambda = 0 written by the build's k_sp_imu_cc
-  // H_cc's column sums inside k_sp_elim1 (the cyclic reduction, no motion-error build cost to add after them)
-  d.cc_fused = (h->use_cr && d.n > 1 && !d.cq && !std::getenv("KSP_CC_SEPARATE")) ? 1 : 0;
+  // H_cc's column sums inside k_sp_elim1 (no motion-error build cost to add after them)
+  d.cc_fused = (d.n > 1 && !d.cq && !std::getenv("KSP_CC_SEPARATE")) ? 1 : 0;
   const int rb = launch_build(h);
   d.zero_lam = 0;
   const int rs = rb ? 0 : launch_solve(h);
@@ -3746,7 +3051,6 @@ kb_sp_handle* kb_sp_create(const kb_sp_layout* L) {
     }
     d.model[i] = L->cam_model[i];
     d.nin[i] = ni;
-    d.col_intr[i] = c;
     for (int q = 0; q < ni; ++q, ++c) {
       d.ckind[c] = 0;
       d.cidx[c] = i;
@@ -3807,49 +3111,8 @@ kb_sp_handle* kb_sp_create(const kb_sp_layout* L) {
   rc |= h->alloc(&d.Lf, (size_t)h->n * NB * NB);
   rc |= h->alloc(&d.Lid, (size_t)h->n * NB);
   rc |= h->alloc(&d.Z, (size_t)h->n * NB * (36 + d.m));
-  rc |= h->alloc(&d.X, (size_t)h->n * NB * d.m);
-  {
-    // partitioned band solve: level 0 is the built system; chunks of 16 nodes, then 8, until <= kSpTop remain
-    const char* ev = std::getenv("KSP_PARTITION");
-    h->use_cr = !(ev && std::atoi(ev) != 0);
-    SpLvl L0{};
-    L0.n = h->n;
-    L0.Dt = d.D0;
-    L0.U = d.U0;
-    L0.Rt = d.R0;
-    L0.Lf = d.Lf;
-    L0.Lid = d.Lid;
-    L0.Z = d.Z;
-    L0.X = d.X;
-    h->lv.push_back(L0);
-    while (h->lv.back().n > kSpTop) {
-      SpLvl& Lc = h->lv.back();
-      Lc.q = Lc.lvl == 0 ? 16 : 8;
-      SpLvl Ln{};
-      Ln.lvl = Lc.lvl + 1;
-      Ln.n = (Lc.n + Lc.q - 1) / Lc.q;
-      const size_t nn = (size_t)Ln.n;
-      double *Dt = nullptr, *Dh = nullptr, *U = nullptr, *Rt = nullptr, *Rh = nullptr;
-      rc |= h->alloc(&Dt, nn * NB * NB);
-      rc |= h->alloc(&Dh, nn * NB * NB);
-      rc |= h->alloc(&U, nn * NB * NB);
-      rc |= h->alloc(&Rt, nn * NB * d.m);
-      rc |= h->alloc(&Rh, nn * NB * d.m);
-      rc |= h->alloc(&Ln.Lf, nn * NB * NB);
-      rc |= h->alloc(&Ln.Lid, nn * NB);
-      rc |= h->alloc(&Ln.Z, nn * NB * (36 + d.m));
-      rc |= h->alloc(&Ln.X, nn * NB * d.m);
-      Ln.Dt = Lc.nDt = Dt;
-      Ln.Dh = Lc.nDh = Dh;
-      Ln.U = Lc.nU = U;
-      Ln.Rt = Lc.nRt = Rt;
-      Ln.Rh = Lc.nRh = Rh;
-      Lc.Xup = Ln.X;
-      if (rc) break;
-      h->lv.push_back(Ln);
-    }
-    h->lv.back().q = h->lv.back().n;
-  }
+  rc |= h->alloc(&d.xs, (size_t)h->n * NB);
+  rc |= h->alloc(&d.bm, (size_t)h->n * NB * 37);
   d.nblk_s = (h->n + NPB - 1) / NPB;
   rc |= h->alloc(&d.spart, (size_t)d.nblk_s * d.Ws);
   rc |= h->alloc(&d.dx, (size_t)h->ncols);
@@ -3882,12 +3145,6 @@ kb_sp_handle* kb_sp_create(const kb_sp_layout* L) {
   }
   h->lds_elim = sizeof(double) * NB * (36 + d.m);
   h->lds_level = 3 * h->lds_elim;
-  h->lds_back = h->lds_elim + sizeof(double) * 3 * NB * d.m;
-  h->lds_back2 = 2 * h->lds_elim + sizeof(double) * 5 * NB * d.m;
-  {
-    const char* ev = std::getenv("KSP_BACK2");  // two back-substitution strides per launch (default on)
-    h->back2 = !(ev && std::atoi(ev) == 0);
-  }
   h->lds_schur = sizeof(double) * (2 * NB * d.m + d.Ws) + sizeof(short2) * d.Ws;
   h->fns_asm[0] = (const void*)k_sp_assemble<false>;
   h->fns_asm[1] = (const void*)k_sp_assemble<true>;
@@ -3915,40 +3172,11 @@ kb_sp_handle* kb_sp_create(const kb_sp_layout* L) {
   hipFuncSetAttribute((const void*)k_sp_level<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                       (int)std::max(h->lds_level, h->lds_schur));
   hipFuncSetAttribute((const void*)k_sp_elim1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_elim);
-  hipFuncSetAttribute((const void*)k_sp_back, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_back);
-  hipFuncSetAttribute((const void*)k_sp_back2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_back2);
-  {
-    // the deep levels in one block (k_sp_deep, KSP_DEEP=1; measured and not kept: configs[4] 2,227 -> 1,998 GN it/s,
-    // the one-block kernel 118 us against 74 us for the six launches it replaces -- four nodes share one CU's SIMDs
-    // and LDS port where each level kernel gives a node a CU of its own, which outweighs the saved launches): as
-    // many node groups as the LDS holds (<= kSpDeepGroups), from the first stride whose level has at most that many
-    // nodes
-    const size_t per = sizeof(double) * kSpDeepPer(d.m);
-    h->deep_groups = (int)std::min<size_t>(kSpDeepGroups, (160 * 1024) / per);
-    h->s_deep = 0;
-    const char* ev = std::getenv("KSP_DEEP");
-    if (h->deep_groups >= 2 && h->n >= 2 && ev && std::atoi(ev) != 0) {
-      int sd = 1;
-      while ((h->n + 2 * sd - 1) / (2 * sd) > h->deep_groups) sd *= 2;
-      h->s_deep = sd;
-      h->lds_deep = per * h->deep_groups;
-      hipFuncSetAttribute((const void*)k_sp_deep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_deep);
-    }
-  }
-  hipFuncSetAttribute((const void*)k_sp_schur, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_schur);
   hipFuncSetAttribute((const void*)k_sp_zschur, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_schur);
   {
-    // the Schur complement from the forward reduction and the one-column back substitution (default with the cyclic
-    // reduction; KSP_ZS=0 keeps the C + 1 column back substitution and X)
-    const char* ev = std::getenv("KSP_ZS");
-    d.zs = (h->use_cr && h->s_deep == 0 && !(ev && std::atoi(ev) == 0)) ? 1 : 0;
     // the Schur sums beside the top level's block (one launch less; KSP_ZSF=0 keeps k_sp_zschur)
     const char* ef = std::getenv("KSP_ZSF");
-    d.zsf = (d.zs && h->n > 1 && !(ef && std::atoi(ef) == 0)) ? 1 : 0;
-    if (d.zs && (h->alloc(&d.xs, (size_t)h->n * NB) || h->alloc(&d.bm, (size_t)h->n * NB * 37))) {
-      kb_sp_destroy(h);
-      return nullptr;
-    }
+    d.zsf = (h->n > 1 && !(ef && std::atoi(ef) == 0)) ? 1 : 0;
   }
   if (hipStreamSynchronize(h->stream) != hipSuccess) {
     fail("kb_sp_create: stream sync failed");
@@ -4533,14 +3761,6 @@ namespace {
 int cov_prepare(kb_sp_handle* h, const char* who) {
   if (!h->built) return fail(std::string(who) + ": build first");
   SpDev& d = h->d;
-  if (!d.zs) {
-    // the factors the recursion reads (Lf, Lid and Z of every node, the top node's included) are complete only after
-    // the default solve
-    const char* why = !h->use_cr       ? "KSP_PARTITION=1 (the partitioned band solve keeps per-chunk factors)"
-                      : h->s_deep != 0 ? "KSP_DEEP=1 (the deep levels' factors stay in the one block's LDS)"
-                                       : "KSP_ZS=0 (the C + 1 column back substitution does not keep the top node's Z)";
-    return fail(std::string(who) + ": no covariance on a handle created under " + why);
-  }
   if (h->cov_ready) return 0;
   const int C = h->C, w = 36 + C, ew = w + NB;
   h->lds_cprep = sizeof(double) * 4 * (NB * NB + NB + NB * (size_t)(ew | 1));
@@ -4785,13 +4005,13 @@ int kb_sp_kernel_stats(kb_sp_handle* h, int32_t n, double* ms_out6, double* fram
     hipLaunchKernelGGL(k_sp_reduce_cc, dim3((d.Wc + 63) / 64), dim3(64 * RW), 0, h->stream, d);
     if (d.cq) hipLaunchKernelGGL(k_sp_mcost_build, dim3(1), dim3(256), 0, h->stream, d);
     KSP_HIP(hipEventRecord(ev[2], h->stream));
-    launch_reduction(h);  // (zs: the forward half; the one-column back substitution follows the camera solve)
+    launch_reduction(h);  // (the forward half; the one-column back substitution follows the camera solve)
     KSP_HIP(hipEventRecord(ev[3], h->stream));
-    if (!d.zsf) hipLaunchKernelGGL(d.zs ? k_sp_zschur : k_sp_schur, dim3(d.nblk_s), dim3(256), h->lds_schur, h->stream, d);
+    if (!d.zsf) hipLaunchKernelGGL(k_sp_zschur, dim3(d.nblk_s), dim3(256), h->lds_schur, h->stream, d);
     hipLaunchKernelGGL(k_sp_schur_red, dim3((d.Ws + 63) / 64), dim3(64 * RW), 0, h->stream, d);
     KSP_HIP(hipLaunchKernel(h->fn_camsolve, dim3(1), dim3(64), args, 0, h->stream));
     KSP_HIP(hipEventRecord(ev[4], h->stream));
-    if (d.zs && launch_bvec(h)) return -1;
+    if (launch_bvec(h)) return -1;
     KSP_HIP(hipEventRecord(ev[5], h->stream));
     hipLaunchKernelGGL(k_sp_update, dim3(d.n), dim3(64), 0, h->stream, d, 1);
     if (launch_cost(h, 1)) return -1;
@@ -4828,7 +4048,7 @@ int kb_sp_kernel_stats(kb_sp_handle* h, int32_t n, double* ms_out6, double* fram
 }  // extern "C"
 
 #ifdef KB_STAMPS
-// diagnostic build only: the KSP_TS timeline (100 MHz ticks) of the last pass
+// diagnostic build only: the KSP_TSB timeline (100 MHz ticks) of the last pass
 extern "C" int kb_sp_diag_read_ts(kb_sp_handle* h, long long* out, int n) {
   if (!h->d.dbg_ts) return fail("kb_sp_diag_read_ts: no stamp buffer");
   KSP_HIP(hipStreamSynchronize(h->stream));

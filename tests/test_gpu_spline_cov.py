@@ -215,24 +215,6 @@ def test_refused_before_build():
         g.close()
 
 
-@pytest.mark.parametrize("env", ["KSP_PARTITION=1", "KSP_ZS=0", "KSP_DEEP=1"])
-def test_refused_on_other_solver_modes(monkeypatch, env):
-    """the factors the recursion reads exist only after the default solve: the refusal names the mode"""
-    k, v = env.split("=")
-    monkeypatch.setenv(k, v)
-    p = SC.problem("n17")
-    g = capi.SplineSolver(p)
-    try:
-        _built(g, p.state_init, 10.0)
-        with pytest.raises(capi.KbError, match=env):
-            g.covariance()
-        with pytest.raises(capi.KbError, match=env):
-            g.curve_covariance(p.frame_time[:2])
-        assert g.solve()[0]  # the handle still solves
-    finally:
-        g.close()
-
-
 @pytest.mark.parametrize("name", ["n4", "n33"])
 def test_schur_sums_in_their_own_launch(monkeypatch, name):
     """KSP_ZSF=0 (k_sp_zschur instead of the top level's extra blocks) is accepted and agrees bitwise with the default.

@@ -174,35 +174,10 @@ def _variant(monkeypatch, env, name, with_pass):
         g.close()
 
 
-@pytest.mark.parametrize("name", ["n2b", "n3", "n4", "n7", "n12", "n33"])
-def test_full_back_substitution(monkeypatch, name):
-    """KSP_ZS=0, the C + 1 column back substitution: 1, 2, 2, 3, 4, 6 strides -- the single top stride and both
-    parities of k_sp_back2's pairing"""
-    _variant(monkeypatch, {"KSP_ZS": "0"}, name, True)
-
-
-@pytest.mark.parametrize("name", ["n7", "n33"])
-def test_full_back_substitution_one_stride_per_launch(monkeypatch, name):
-    _variant(monkeypatch, {"KSP_ZS": "0", "KSP_BACK2": "0"}, name, True)
-
-
 @pytest.mark.parametrize("name", ["n2b", "n4", "n33"])
 def test_schur_sums_in_their_own_launch(monkeypatch, name):
     """KSP_ZSF=0: k_sp_zschur instead of the extra blocks of the top level"""
     _variant(monkeypatch, {"KSP_ZSF": "0"}, name, True)
-
-
-@pytest.mark.parametrize("name", ["n12", "n17", "n33", "n65", "c64"])
-def test_partitioned_band_solve(monkeypatch, name):
-    """KSP_PARTITION=1 (k_sp_chunk / k_sp_ctop / k_sp_cback): no chunk level (n = 12), two chunks with a one-node
-    second (17), three (33), chunks of 16 with a one-node tail (65), the widest camera block"""
-    _variant(monkeypatch, {"KSP_PARTITION": "1"}, name, True)
-
-
-@pytest.mark.parametrize("name", ["n2b", "n4", "n17", "n65"])
-def test_deep_levels(monkeypatch, name):
-    """KSP_DEEP=1: the reduction's deep levels in one block (with the C + 1 column back substitution)"""
-    _variant(monkeypatch, {"KSP_DEEP": "1"}, name, True)
 
 
 @pytest.mark.parametrize("name", ["n4", "n33"])

@@ -1,6 +1,6 @@
 """Diagnostic: timeline of the cyclic reduction of one GN pass at configs[4] (KSP_TSB stamps, s_memrealtime 100 MHz):
-k_sp_elim1 (block 1), every k_sp_level (block 1, or 0 when alone) and k_sp_back (block 0), phase by phase, and the
-gap from one launch's stamped block end to the next launch's stamped block entry.  Diagnostic library only:
+k_sp_elim1 (block 1) and every k_sp_level (block 1, or 0 when alone), phase by phase, and the gap from one launch's
+stamped block end to the next launch's stamped block entry.  Diagnostic library only:
 python tools/diag_sp_levels.py"""
 import ctypes as C
 import os
@@ -31,10 +31,6 @@ for rep in range(3):
         st = [buf[120 + 6 * lv + k] for k in range(5)]
         if st[0] >= t0 and st[4] >= st[0] and st[0] > 0:
             rows.append((f"level s={1 << lv}", st, ["staged", "products", "chol", "fwd+store"]))
-    for lv in reversed(range(11)):
-        st = [buf[190 + 4 * lv + k] for k in range(4)]
-        if st[0] >= t0 and st[3] >= st[0] and st[0] > 0:
-            rows.append((f"back s={1 << lv}", st, ["staged", "T (MFMA)", "solve+store"]))
     print(f"rep {rep}: cyclic reduction of the last GN pass, us from k_sp_elim1 entry")
     prev_end = None
     tot_gap = 0.0
